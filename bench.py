@@ -20,7 +20,16 @@ pooling, recording).  value = chains x groups x iterations / second over the who
 (max over ranks of the timed region); no collective in the loop, one RCCL gather of the
 sample stores after the timed region.
 
-Launch:  python bench.py [--workload cfg3] [--gpus N --steps K --warmup W]
+A plain run sets up, warms up, times the K steps and prints the result line (metric,
+value, unit, ms_per_step, ...).  ``--full`` adds every other leg: the CPU baseline, the two
+rocprofv3 PMC passes (HBM traffic), the kernel-timing pass behind the roofline figures and,
+on N > 1 ranks, the timed RCCL gather (``--no-pmc``, ``--cpu-seconds`` and ``--no-gather``
+trim those legs and mean nothing without ``--full``).  ``--dump-outputs DIR`` writes what
+the timed call left -- the sample row of its last step and the chain state after it -- as
+DIR/<name>.npy; the inputs are seeded, so two builds can be compared array for array.
+
+Launch:  python bench.py [--workload cfg3] [--gpus N --steps K --warmup W] [--full]
+         [--dump-outputs DIR]
          (N > 1: python -m torch.distributed.run --nproc-per-node N ... bench.py; the host
          bootstrap is nestmc.parallel.HostGroup, no PyTorch)
 """
@@ -94,13 +103,21 @@ def parse():
     ap.add_argument("--warmup", type=int, default=200)
     ap.add_argument("--chains", type=int, default=None,
                     help="chains per GPU (weak workloads) or in total (strong ones)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline figure: CPU baseline, PMC "
+                         "traffic passes, kernel-timing pass (roofline), RCCL gather")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the timed call's last sample row and the state after it as "
+                         "DIR/<name>.npy (float64)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0,
-                    help="timed window of the CPU baseline sample (0 disables)")
-    ap.add_argument("--no-gather", action="store_true")
+                    help="(--full) timed window of the CPU baseline sample (0 disables)")
+    ap.add_argument("--no-gather", action="store_true",
+                    help="(--full) skip the RCCL gather of the sample stores")
     ap.add_argument("--no-resident", action="store_true",
                     help="a new step launch per call (nmc_set_resident off; the A/B)")
     ap.add_argument("--no-pmc", action="store_true",
-                    help="skip the two rocprofv3 PMC passes that measure HBM traffic")
+                    help="(--full) skip the two rocprofv3 PMC passes that measure HBM "
+                         "traffic")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--spawn-dry-run", action="store_true",
                     help="(tests) every spawned rank prints its shard and exits before any "
@@ -455,12 +472,12 @@ def spawn_ranks(args):
     """``--gpus N`` (N > 1) without a launcher: this process starts N ranks itself, one per
     GPU, as child processes with the torchrun environment (RANK / LOCAL_RANK / WORLD_SIZE /
     MASTER_ADDR / MASTER_PORT) -- before it makes any HIP call -- and relays rank 0's JSON
-    line; any failed rank fails the run.  The CPU-baseline leg runs here, before the
-    spawn, and is attached to the line (the ranks skip it and the PMC passes).  Replaces the
+    line; any failed rank fails the run.  The CPU-baseline leg (``--full``) runs here, before
+    the spawn, and is attached to the line (the ranks skip it and the PMC passes).  Replaces the
     reference's process fan-out (posteriorSampling.py:182-201) at the GPU level."""
     import subprocess
     cpu = None
-    if args.cpu_seconds > 0 and not args.spawn_dry_run:
+    if args.full and args.cpu_seconds > 0 and not args.spawn_dry_run:
         try:
             cpu = cpu_baseline(args.wl, args.cpu_seconds)
         except Exception as e:
@@ -530,10 +547,10 @@ def main():
                           "chains_total": job_chains(wl, world), "scaling": wl["scaling"],
                           "libnestmc_mapped": "libnestmc" in open("/proc/self/maps").read()}))
         return 0
-    # host-side legs first, before this process initialises the GPU: the PMC passes
-    # run this script as rocprofv3 children, the CPU baseline forks a process pool
+    # host-side legs of a --full run first, before this process initialises the GPU: the
+    # PMC passes run this script as rocprofv3 children, the CPU baseline forks a process pool
     pmc, cpu = None, None
-    if world == 1:
+    if args.full and world == 1:
         if not args.no_pmc:
             try:
                 pmc = measure_traffic(args)
@@ -605,18 +622,23 @@ def main():
     t_max = parallel.max_over_ranks(t_rank, hg)
     c_total = job_chains(wl, world)
 
-    # second pass, same length: per-launch events on the engine's stream -> the
-    # step kernel's average duration for the roofline
-    eng.set_kernel_timing(True)
-    eng.run(W + K, W + 2 * K)
-    kt = eng.kernel_timing()
-    eng.set_kernel_timing(False)
+    if args.dump_outputs:
+        dump_outputs(eng, args.dump_outputs, K, rank, world)
+
+    kt = None
+    if args.full:
+        # second pass, same length: per-launch events on the engine's stream -> the
+        # step kernel's average duration for the roofline
+        eng.set_kernel_timing(True)
+        eng.run(W + K, W + 2 * K)
+        kt = eng.kernel_timing()
+        eng.set_kernel_timing(False)
     # (G > 128: launches whose step kernel updated its own Gibbs tasks because the Gibbs
     #  kernel did not run beside it -- 0 when the two kernels were co-scheduled)
     gibbs_fb = eng.gibbs_fallbacks()
 
     gather_ms, gather_err = None, None
-    if world > 1 and not args.no_gather:
+    if args.full and world > 1 and not args.no_gather:
         # after the timed region: the one RCCL gather of the sample stores; a
         # failure here is reported in the line, never lost with it
         try:
@@ -632,12 +654,86 @@ def main():
     G, N, P = wl["groups"], wl["obs"], fam.n_params
     units = c_total * G * K
     value = units / t_max
+    lc = eng.launch_config()
+    # the roofline figures need the kernel-timing pass: a --full run only
+    roof = None if kt is None else roofline(args, wl, fam, C, kt, lc["kernel"], pmc)
+
+    if rank == 0:
+        desc = wl["desc"] % (wl["chains"], G, N, P)
+        out = {
+            "metric": METRIC,
+            "value": value,
+            "unit": "chain*group*iter/s",
+            "n_gpus": world,
+            "steps": K,
+            "warmup": W,
+            "ms_per_step": t_max * 1e3 / K,
+            "higher_is_better": True,
+            "scaling": wl["scaling"],
+            "vs_baseline": None,
+            "dtype": "f64",
+            "data": "synthetic",
+            "full": bool(args.full),
+            "config": {"workload": desc, "name": args.workload,
+                       "chains_total": c_total, "chains_per_gpu": C, "groups": G,
+                       "obs_per_group": N, "params": P, "pooling": wl["pooling"],
+                       "parallelism": "chains sharded x%d" % world, "launch": lc,
+                       "recorded_iters_in_timed_region": recorded_in(W, W + K, n_iter, burn,
+                                                                     thin),
+                       "gibbs_fallbacks": gibbs_fb,
+                       # the timed call ran inside the resident launch the warm-up started
+                       # (its GPU span is event_ms); the kernel-timing pass and the PMC
+                       # passes use separate launches of the same K iterations
+                       "resident": dict(res1, timed_call_resident=res1["calls"] > 0)},
+            "roofline": roof,
+            "cpu_baseline": cpu,
+            "event_ms": ev_ms,
+            "wall_ms": wall * 1e3,
+            "enqueue_ms": t_enq * 1e3,
+            "hyper_only_avg_us": None if kt is None else
+            (kt["hyper_ms"] / max(1, kt["hyper_launches"])) * 1e3,
+            "gather_ms": gather_ms,
+            "gather_error": gather_err,
+            "variate_fill": fill,
+            "outputs": args.dump_outputs,
+        }
+        print(json.dumps(out))
+    eng.close()
+    if hg is not None:
+        hg.barrier()
+        hg.close()
+
+
+def dump_outputs(eng, out_dir, K, rank, world):
+    """``--dump-outputs``: what the timed call [W, W + K) computed in its last step, as a
+    caller of the engine receives it -- the sample row that step recorded (row K - 1 of the
+    store: the burn-in is the warm-up and the thinning 1) and the chain state after it --
+    one float64 DIR/<name>.npy each (<name>.rank<r>.npy on N > 1 ranks).  A few hundred KB
+    per array at the shipped workloads; more than 64 MB in all is refused, not cut."""
+    os.makedirs(out_dir, exist_ok=True)
+    row = eng.samples_raw(K - 1, 1)[0]                    # [cols][C]
+    arrays = {"sample_row": numpy.ascontiguousarray(row.T)}      # [C, cols]
+    st = eng.get_state()
+    for name in ("value", "log_prior", "ll", "scale"):
+        arrays["state_" + name] = st[name]
+    if eng.pooling == "partial":
+        arrays["state_mu"], arrays["state_s2"] = st["mu"], st["s2"]
+    total = sum(a.nbytes for a in arrays.values())
+    if total > 64 << 20:
+        raise SystemExit("bench.py: --dump-outputs would write %d bytes (limit 64 MB)" % total)
+    suffix = ".npy" if world == 1 else ".rank%d.npy" % rank
+    for name, a in arrays.items():
+        numpy.save(os.path.join(out_dir, name + suffix), numpy.asarray(a, dtype=numpy.float64))
+
+
+def roofline(args, wl, fam, C, kt, kname, pmc):
+    """The ``roofline`` entry of a --full line, from the kernel-timing pass ``kt`` (and the
+    PMC passes' bytes when they ran)."""
+    G, N, P = wl["groups"], wl["obs"], fam.n_params
     launches = kt["step_launches"]
     avg_step_ms = kt["step_ms"] / max(1, launches)
     iters_per_launch = kt["step_iters"] / max(1, launches)
     b_obs = fam.bytes_per_obs()
-    lc = eng.launch_config()
-    kname = lc["kernel"]
     inst = fam_instance(kname)
     # SURVEY 8(d): B_unit = P*N*b_obs per chain*group*iteration (each parameter step
     # evaluates the group's rows once per chain), for THIS rank's chains per launch
@@ -663,76 +759,36 @@ def main():
         traffic = pmc["bytes_per_launch"] * iters_per_launch / pmc["iterations_per_launch"]
         hbm_meas = traffic / (avg_step_ms * 1e-3) / 1e9
 
-    if rank == 0:
-        desc = wl["desc"] % (wl["chains"], G, N, P)
-        out = {
-            "metric": METRIC,
-            "value": value,
-            "unit": "chain*group*iter/s",
-            "n_gpus": world,
-            "steps": K,
-            "warmup": W,
-            "ms_per_step": t_max * 1e3 / K,
-            "higher_is_better": True,
-            "scaling": wl["scaling"],
-            "vs_baseline": None,
-            "dtype": "f64",
-            "data": "synthetic",
-            "config": {"workload": desc, "name": args.workload,
-                       "chains_total": c_total, "chains_per_gpu": C, "groups": G,
-                       "obs_per_group": N, "params": P, "pooling": wl["pooling"],
-                       "parallelism": "chains sharded x%d" % world, "launch": lc,
-                       "recorded_iters_in_timed_region": recorded_in(W, W + K, n_iter, burn,
-                                                                     thin),
-                       "gibbs_fallbacks": gibbs_fb,
-                       # the timed call ran inside the resident launch the warm-up started
-                       # (its GPU span is event_ms); the kernel-timing pass and the PMC
-                       # passes use separate launches of the same K iterations
-                       "resident": dict(res1, timed_call_resident=res1["calls"] > 0)},
-            "roofline": {"bound": "valu", "achieved": valu_tips, "peak": VALU_PEAK_TIPS,
-                         "unit": "T fp64 lane-instr/s",
-                         "frac": None if valu_tips is None else valu_tips / VALU_PEAK_TIPS,
-                         "traffic": traffic,
-                         "kernel": kname,
-                         "avg_launch_us": avg_step_ms * 1e3,
-                         "iterations_per_launch": iters_per_launch,
-                         "valu_per_chain_row": per_row,
-                         "valu_lane_instr_per_launch": lane_instr_per_launch,
-                         "derivation": "achieved = C*G*P*N*valu_per_chain_row fp64 VALU "
-                                       "lane-instructions per iteration (the shipped row loop "
-                                       "of this family instance, counted in its ISA) x "
-                                       "iterations_per_launch / avg_launch_us (this rank's "
-                                       "chains); peak = 256 CUs x 4 SIMDs x 16 fp64 lanes x "
-                                       "2.4 GHz (78.6 TFLOP/s fp64 / 2)",
-                         "lds": {"delivered_gbs": lds_gbs, "peak": LDS_PEAK_GBS,
-                                 "frac": lds_gbs / LDS_PEAK_GBS,
-                                 "note": "bytes the row loop's LDS reads deliver (paired loop: "
-                                         "one read serves a row pair to 64 lanes = 2 chains per "
-                                         "row, half of C*G*P*N*b_obs)"},
-                         "hbm": {"algorithmic_gbs": achieved_gbs, "peak": HBM_PEAK_GBS,
-                                 "algorithmic_frac": achieved_gbs / HBM_PEAK_GBS,
-                                 "measured_gbs": hbm_meas,
-                                 "measured_frac": None if hbm_meas is None
-                                 else hbm_meas / HBM_PEAK_GBS,
-                                 "note": "SURVEY 8(d) prices the path at HBM; the rows are "
-                                         "read from HBM once per launch and served from LDS, "
-                                         "so the algorithmic frac exceeds 1 by construction; "
-                                         "measured = PMC bytes of the same launch"},
-                         "pmc": pmc},
-            "cpu_baseline": cpu,
-            "event_ms": ev_ms,
-            "wall_ms": wall * 1e3,
-            "enqueue_ms": t_enq * 1e3,
-            "hyper_only_avg_us": (kt["hyper_ms"] / max(1, kt["hyper_launches"])) * 1e3,
-            "gather_ms": gather_ms,
-            "gather_error": gather_err,
-            "variate_fill": fill,
-        }
-        print(json.dumps(out))
-    eng.close()
-    if hg is not None:
-        hg.barrier()
-        hg.close()
+    return {"bound": "valu", "achieved": valu_tips, "peak": VALU_PEAK_TIPS,
+            "unit": "T fp64 lane-instr/s",
+            "frac": None if valu_tips is None else valu_tips / VALU_PEAK_TIPS,
+            "traffic": traffic,
+            "kernel": kname,
+            "avg_launch_us": avg_step_ms * 1e3,
+            "iterations_per_launch": iters_per_launch,
+            "valu_per_chain_row": per_row,
+            "valu_lane_instr_per_launch": lane_instr_per_launch,
+            "derivation": "achieved = C*G*P*N*valu_per_chain_row fp64 VALU "
+                          "lane-instructions per iteration (the shipped row loop "
+                          "of this family instance, counted in its ISA) x "
+                          "iterations_per_launch / avg_launch_us (this rank's "
+                          "chains); peak = 256 CUs x 4 SIMDs x 16 fp64 lanes x "
+                          "2.4 GHz (78.6 TFLOP/s fp64 / 2)",
+            "lds": {"delivered_gbs": lds_gbs, "peak": LDS_PEAK_GBS,
+                    "frac": lds_gbs / LDS_PEAK_GBS,
+                    "note": "bytes the row loop's LDS reads deliver (paired loop: "
+                            "one read serves a row pair to 64 lanes = 2 chains per "
+                            "row, half of C*G*P*N*b_obs)"},
+            "hbm": {"algorithmic_gbs": achieved_gbs, "peak": HBM_PEAK_GBS,
+                    "algorithmic_frac": achieved_gbs / HBM_PEAK_GBS,
+                    "measured_gbs": hbm_meas,
+                    "measured_frac": None if hbm_meas is None
+                    else hbm_meas / HBM_PEAK_GBS,
+                    "note": "SURVEY 8(d) prices the path at HBM; the rows are "
+                            "read from HBM once per launch and served from LDS, "
+                            "so the algorithmic frac exceeds 1 by construction; "
+                            "measured = PMC bytes of the same launch"},
+            "pmc": pmc}
 
 
 if __name__ == "__main__":

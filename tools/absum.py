@@ -1,4 +1,5 @@
-"""One line per bench JSON (A/B runs): value, launch time, iterations per launch, kernel."""
+"""One line per ``bench.py --full`` JSON (A/B runs): value, launch time, iterations per
+launch, kernel."""
 import json
 import sys
 

@@ -8,7 +8,7 @@
 #   tests[:EXPR]        pytest -m gpu [-k EXPR]                      TAG_tests.txt
 #   tfile:FILE[:EXPR]   pytest FILE -m gpu [-k EXPR]                 TAG_tests.txt (appended)
 #   smoke               __graft_entry__.smoke()                      TAG_smoke.txt
-#   bench:ARGS          python bench.py ARGS (ARGS: commas for spaces) TAG_bench.jsonl (appended)
+#   bench:ARGS          python bench.py --full ARGS (ARGS: commas for spaces) TAG_bench.jsonl (appended)
 #   kstats:ARGS         rocprofv3 --kernel-trace --stats of bench.py ARGS   TAG_kstats/
 #   pmc:CTR[+CTR]:ARGS  rocprofv3 --pmc CTR ... of bench.py ARGS     TAG_pmc_<n>/
 #   py:SCRIPT[:ARGS]    python SCRIPT ARGS                           TAG_py.txt (appended)
@@ -50,7 +50,7 @@ for task in "$@"; do
       tail -2 "$OUT/${TAG}_smoke.txt" ;;
     bench)
       args=${rest//,/ }
-      timeout -k 10 600 python -u bench.py $args > "$OUT/${TAG}_bench.tmp" 2> "$OUT/${TAG}_bench.err" || {
+      timeout -k 10 600 python -u bench.py --full $args > "$OUT/${TAG}_bench.tmp" 2> "$OUT/${TAG}_bench.err" || {
         tail -20 "$OUT/${TAG}_bench.err"; exit 1; }
       grep '^{' "$OUT/${TAG}_bench.tmp" >> "$OUT/${TAG}_bench.jsonl"
       python -c "import json,sys; d=json.loads(open(sys.argv[1]).read().splitlines()[-1]); \

@@ -1,12 +1,12 @@
 #!/usr/bin/env python
 """HBM traffic per launch of the iteration kernel from two rocprofv3 PMC passes.
 
-    rocprofv3 --pmc FETCH_SIZE -d gpurun_out/pmc_fetch -o run -- python3 bench.py ...
-    rocprofv3 --pmc WRITE_SIZE -d gpurun_out/pmc_write -o run -- python3 bench.py ...
-    python tools/hbm_traffic.py gpurun_out/pmc_fetch gpurun_out/pmc_write ITERS > profiles/...json
+    rocprofv3 --pmc FETCH_SIZE -d OUT/pmc_fetch -o run -- python3 bench.py --full --no-pmc ...
+    rocprofv3 --pmc WRITE_SIZE -d OUT/pmc_write -o run -- python3 bench.py --full --no-pmc ...
+    python tools/hbm_traffic.py OUT/pmc_fetch OUT/pmc_write ITERS > profiles/...json
 
-ITERS: iterations the profiled run's step launches covered (bench.py --steps K
---warmup W runs W + 2K), so the bytes can be normalised per iteration.
+ITERS: iterations the profiled run's step launches covered (bench.py --full --steps K
+--warmup W runs W + 2K, a plain run W + K), so the bytes can be normalised per iteration.
 
 FETCH_SIZE and WRITE_SIZE are collected in separate passes (MI355X_MICROARCH.md
 "rocprofv3 PMC slots": they do not fit one TCC pass) and are reported by rocprofv3
