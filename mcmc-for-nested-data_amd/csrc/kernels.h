@@ -1223,7 +1223,10 @@ __device__ __forceinline__ void nmc_ll_rows_staged(const Fam& fam, const typenam
   for (int s = 0; s < 4; ++s)
 #pragma unroll
     for (int k = 0; k < Fam::NACC; ++k) a[s][k] = 0.0;
-  const uintptr_t last = ((uintptr_t)lim - 16) & ~(uintptr_t)15;   // last whole 16 B of the group
+  // the aligned 16 B that hold the group's last double: when the group ends on an odd double
+  // offset (odd NF x odd row count) they reach 8 B into the next group, or into the slack
+  // that nmc_create allocates behind the table
+  const uintptr_t last = ((uintptr_t)lim - 8) & ~(uintptr_t)15;
   auto issue = [&](int c, double* buf) -> int {   // chunk c -> buf; returns its offset (doubles)
     const uintptr_t src = (uintptr_t)(p + (size_t)c * SR * NF);
     const uintptr_t a16 = src & ~(uintptr_t)15;

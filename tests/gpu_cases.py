@@ -90,12 +90,13 @@ def partial_state(fam, sizes, C, P, seed=11, spread=1.0):
 
 def run_engine(fam, sizes, st, sel, chain_base, n_iter, seed, pooling="partial", priors=None,
                env=None, burn=None, thin=1, tune_interval=5, launch_iters=0, calls=None,
-               resident=False):
+               resident=False, scale=None):
     """Run the HIP engine on chains ``sel`` of state ``st``; returns
     (accept flags [C, iter, P, G], proposal LLs, recorded rows [C, rows, cols], launch config).
     calls: the engine calls in order, ("run" | "prefill", i0, i1), ("synchronize", 0, 0),
     ("sleep", ms, 0) or ("get_state", 0, 0) (default: one run).  resident: nmc_set_resident
-    (launch config: "resident" stats, "state" the final get_state, "accept" the counts)."""
+    (launch config: "resident" stats, "state" the final get_state, "accept" the counts).
+    scale: proposal scales [C, P, G] of all chains of ``st`` (default: the engine's ones)."""
     import os
     from nestmc.engine import Engine
     old = {}
@@ -112,7 +113,8 @@ def run_engine(fam, sizes, st, sel, chain_base, n_iter, seed, pooling="partial",
                 os.environ[k] = v
     mu = None if st.mu is None else st.mu[sel]
     s2 = None if st.s2 is None else st.s2[sel]
-    eng.set_state(st.value[sel], st.lp[sel], st.ll[sel], mu, s2)
+    eng.set_state(st.value[sel], st.lp[sel], st.ll[sel], mu, s2,
+                  scale=None if scale is None else numpy.asarray(scale)[sel])
     eng.set_schedule(n_iter, n_iter // 2 if burn is None else burn, thin,
                      tune_interval=tune_interval)
     eng.set_trace(True)
@@ -145,13 +147,16 @@ def run_engine(fam, sizes, st, sel, chain_base, n_iter, seed, pooling="partial",
 
 
 def run_oracle(nested, st, sel, chain_ids, n_iter, seed, pooling="partial", priors=None,
-               burn=None, thin=1, tune_interval=5):
-    """The numpy oracle on the same Philox stream for chains ``sel`` (global ids chain_ids)."""
+               burn=None, thin=1, tune_interval=5, scale=None):
+    """The numpy oracle on the same Philox stream for chains ``sel`` (global ids chain_ids);
+    scale: proposal scales [C, P, G] of all chains of ``st`` (default ones)."""
     from oracle import restatement as rs
     C = len(sel)
     o = rs.State(st.value[sel].copy(), st.lp[sel].copy(), st.ll[sel].copy(),
                  None if st.mu is None else st.mu[sel].copy(),
                  None if st.s2 is None else st.s2[sel].copy())
+    if scale is not None:
+        o.scale = numpy.array(numpy.asarray(scale)[sel], float)
     P, G = o.value.shape[1], o.value.shape[2]
     trace, rec = {}, []
     rs.run(nested, o, pooling, priors, n_iter, n_iter // 2 if burn is None else burn, thin,
