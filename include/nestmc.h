@@ -79,7 +79,8 @@ int nmc_device_count(int* n);
  *                                                     const double* k);     // consts
  * returning ONE observation's log-likelihood (the reference's logLikelihoodFunction,
  * posteriorSampling.py:61-102, evaluated per row); include_dir = the library's csrc
- * directory (kernels.h, fam_user.h).  *family_id -> pass as nmc_create's ll_family.
+ * directory (kernels.h and its parts, fam_user.h).  *family_id -> pass as nmc_create's
+ * ll_family.
  * Errors carry the compiler log (nmc_last_error).                                  */
 int nmc_user_family_compile(const char* source, int n_fields, int n_params,
                             const char* include_dir, int* family_id);

@@ -8,6 +8,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <stdlib.h>
+
 #include <algorithm>
 #include <chrono>
 #include <string>
@@ -17,6 +19,24 @@
 #include "../../include/nestmc.h"
 #include "kernels.h"
 #include "sweep.h"
+
+// Run-time knobs: the NMC_* environment variables (the knob table).  Integer
+// and on/off knobs are read through these two; a knob that is text, a byte count or a time
+// (NMC_ROWS, NMC_*_BYTES, NMC_*_US), or that matters by being set at all, reads getenv itself.
+static inline int nmc_env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : dflt;
+}
+static inline bool nmc_env_flag(const char* name, bool dflt) {
+  const char* e = getenv(name);
+  return e ? atoi(e) != 0 : dflt;
+}
+// NMC_PERSIST (tests, A/B): 1 / 0 forces the answer of the families' "may the whole grid be
+// resident" query (NMC_OP_CAN_PERSIST); -1: unset, the occupancy decides
+static inline int nmc_env_persist() {
+  const char* e = getenv("NMC_PERSIST");
+  return e ? (atoi(e) != 0 ? 1 : 0) : -1;
+}
 
 // error message of the calling thread (nestmc.hip); returns code
 int nmc_fail(int code, const std::string& msg);
@@ -83,7 +103,7 @@ struct nmc_ctx {
   double* user_k = nullptr;               // user family: device copy of the model constants
   bool sweep = false;                     // nmc_k_sweep runs the loop (choose_geometry)
   bool no_sweep = false;                  // (its grid could not be resident: nmc_k_run)
-  // Resident launch (nmc_set_resident; kernels.h Dev.rcmd): one step launch serves the
+  // Resident launch (nmc_set_resident; dev.h Dev.rcmd): one step launch serves the
   // consecutive nmc_run calls of a sampling loop; any other entry point parks it first.
   struct Resident {
     bool on = false;                      // requested and possible for this context

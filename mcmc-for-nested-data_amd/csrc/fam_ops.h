@@ -58,7 +58,7 @@ static int nmc_launch_run(nmc_ctx* x, const Fam& fam, int i0, int i1, int flags,
 // persistent kernel's chain-block waits need it.)
 template <class Fam>
 static bool nmc_can_persist(nmc_ctx* x) {
-  if (const char* e = getenv("NMC_PERSIST")) return atoi(e) != 0;
+  if (const int f = nmc_env_persist(); f >= 0) return f != 0;
   int nb = 0;
   const void* k = nmc_run_kernel<Fam>(x, nmc_persist_mode(x));
   if (!k || hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, 64 * x->d.W,

@@ -67,18 +67,12 @@ static void choose_geometry(nmc_ctx* x) {
   // the wave count from the rows alone: the none/complete-pooling tile balance below sizes
   // the tiles from it, so the NMC_WAVES override never changes a sum
   const int64_t w_rows = w;
-  if (const char* e = getenv("NMC_WAVES")) {
-    const int v = atoi(e);
-    if (v >= 1 && v <= NMC_RUN_THREADS / 64) w = v;
-  }
+  if (const int v = nmc_env_int("NMC_WAVES", 0); v >= 1 && v <= NMC_RUN_THREADS / 64) w = v;
   d.RB = (d.C + d.CL - 1) / d.CL;
   d.W = (int)w;
   d.tile = 64;   // rows per likelihood tile (a multiple of 16)
 #ifdef NMC_DEBUG_KNOBS   // (diagnostic builds only: changes the summation order)
-  if (const char* e = getenv("NMC_TILE_ROWS")) {
-    const int v = atoi(e);
-    if (v >= 16 && v % 16 == 0) d.tile = v;
-  }
+  if (const int v = nmc_env_int("NMC_TILE_ROWS", 0); v >= 16 && v % 16 == 0) d.tile = v;
 #endif
   // partial pooling, persistent payload-in-LDS mode: wave 1 is the Gibbs wave
   d.naux = x->pooling == NMC_POOL_PARTIAL && d.W >= 3 && d.nleaf <= 4 ? 1 : 0;
@@ -86,27 +80,26 @@ static void choose_geometry(nmc_ctx* x) {
   d.rows_lds = (size_t)d.nmax * x->nf * 8 <= (size_t)64 * 1024 &&
                lds_bytes_for(x, 0, 1) <= (size_t)96 * 1024;
 #ifdef NMC_DEBUG_KNOBS   // (diagnostic builds only: the scalar-load row loop's blocks differ)
-  if (getenv("NMC_NO_LDS_ROWS") && atoi(getenv("NMC_NO_LDS_ROWS"))) d.rows_lds = 0;
+  if (nmc_env_flag("NMC_NO_LDS_ROWS", false)) d.rows_lds = 0;
 #endif
 
   // the persistent Gibbs update by the auxiliary waves needs G <= 128 (one numpy
   // leaf) and one parameter's chain-block values in LDS
-  d.noprio = getenv("NMC_NOPRIO") ? atoi(getenv("NMC_NOPRIO")) : 0;   // diagnostics bits
-  d.ctiles = getenv("NMC_CTL_TILES") ? atoi(getenv("NMC_CTL_TILES")) : 1;   // (Dev.ctiles)
-  d.gtiles = getenv("NMC_GIBBS_TILES") ? atoi(getenv("NMC_GIBBS_TILES")) : 1;   // (Dev.gtiles)
+  d.noprio = nmc_env_int("NMC_NOPRIO", 0);       // diagnostics bits
+  d.ctiles = nmc_env_int("NMC_CTL_TILES", 1);    // (Dev.ctiles)
+  d.gtiles = nmc_env_int("NMC_GIBBS_TILES", 1);  // (Dev.gtiles)
   d.pubearly = 0;   // (Dev.pubearly: set with the geometry, NMC_PUB_EARLY overrides)
   d.gwaves = 4;   // (waves of nmc_k_sweep_gibbs)
-  d.nstatic = getenv("NMC_STATIC_TILES") ? atoi(getenv("NMC_STATIC_TILES")) != 0 : 1;
+  d.nstatic = nmc_env_flag("NMC_STATIC_TILES", true);
   d.hlds = d.naux > 0 && d.G <= 128 && lds_bytes_for(x, 1, d.rows_lds) <= (size_t)160 * 1024 &&
-           !(getenv("NMC_NO_HLDS") && atoi(getenv("NMC_NO_HLDS")));
+           !nmc_env_flag("NMC_NO_HLDS", false);
   // G <= 64: the Gibbs wave fetches a task's values into registers (one sc1 round trip)
   // and updates in the step after publication (no LDS payload, no two-stage pipeline).
   // (An owner hand-off for 64 < G -- one workgroup's Gibbs wave updating each task once
   //  for its chain block, the others reading its results -- measured slower, 62 against
   //  53 us/iter at the cfg-4 shard, and was removed in round 5; G > 128 runs nmc_k_sweep's
   //  Gibbs workgroups, which do the same with whole workgroups.)
-  d.hreg = d.naux > 0 && d.G <= 64 && d.hlds &&
-           !(getenv("NMC_NO_HREG") && atoi(getenv("NMC_NO_HREG")));
+  d.hreg = d.naux > 0 && d.G <= 64 && d.hlds && !nmc_env_flag("NMC_NO_HREG", false);
   // Partial pooling whose grid is more than one 8-wave workgroup per CU but fits two
   // 4-wave ones (cfg-4 shards: 2 chain blocks x 256 groups): four waves, so the whole
   // grid is resident and runs persistent (both chain blocks' workgroups share each CU
@@ -121,12 +114,12 @@ static void choose_geometry(nmc_ctx* x) {
     }
   }
   // likelihood rows in LDS for a family whose row blocks pair up (<= 4 fields): each lane
-  // evaluates its rows for two chains (kernels.h nmc_ll_rows_lds<Fam, true>), half the LDS
+  // evaluates its rows for two chains (rows.h nmc_ll_rows_lds<Fam, true>), half the LDS
   // reads; NMC_ROWS=bcast keeps the one-chain broadcast loop (same sums bit for bit)
   d.paired = d.rows_lds && x->nf <= 4;
   if (const char* e = getenv("NMC_ROWS")) d.paired = d.paired && strcmp(e, "bcast") != 0;
   // {x, y} rows (linear regression with one covariate): four chains per lane instead
-  // (kernels.h nmc_ll_rows_lds_quad, nmc_k_run only), the same sums bit for bit;
+  // (rows.h nmc_ll_rows_lds_quad, nmc_k_run only), the same sums bit for bit;
   // NMC_ROWS=pair keeps the paired loop
   d.quad = d.paired && x->family == NMC_LL_LINREG && x->nf == 2;
   if (const char* e = getenv("NMC_ROWS")) d.quad = d.quad && strcmp(e, "pair") != 0;
@@ -136,7 +129,7 @@ static void choose_geometry(nmc_ctx* x) {
   // the paired loop's two row parities (NMC_MODE_HALF) -- twice the workgroups, the same
   // sums bit for bit.  NMC_HALF=0 keeps 64 chains per workgroup (tests compare them).
   if (x->pooling != NMC_POOL_PARTIAL && d.S == 1 && d.paired &&
-      (int64_t)d.RB * d.G * 2 <= x->ncu && !(getenv("NMC_HALF") && !atoi(getenv("NMC_HALF")))) {
+      (int64_t)d.RB * d.G * 2 <= x->ncu && nmc_env_flag("NMC_HALF", true)) {
     d.CL = 32;
     d.RB = (d.C + d.CL - 1) / d.CL;
   }
@@ -151,7 +144,7 @@ static void choose_geometry(nmc_ctx* x) {
   // NMC_TILE_BALANCE=0 (64-row tiles) changes sums and exists in diagnostic builds only.
   bool balance = true;
 #ifdef NMC_DEBUG_KNOBS
-  if (getenv("NMC_TILE_BALANCE") && !atoi(getenv("NMC_TILE_BALANCE"))) balance = false;
+  balance = nmc_env_flag("NMC_TILE_BALANCE", true);
 #endif
   if (x->pooling != NMC_POOL_PARTIAL && d.S == 1 && w_rows >= 3 && balance) {
     const int64_t wt = w_rows - 1, n = d.nmax, t64 = (n + 63) / 64;
@@ -173,17 +166,14 @@ static void choose_geometry(nmc_ctx* x) {
   x->sweep = false;
   d.gsep = 0;
   const bool sweep_want = x->pooling == NMC_POOL_PARTIAL && d.G > 128 && d.nleaf <= 4 &&
-                          x->family < NMC_LL_USER_BASE &&
-                          !(getenv("NMC_SWEEP") && !atoi(getenv("NMC_SWEEP")));
+                          x->family < NMC_LL_USER_BASE && nmc_env_flag("NMC_SWEEP", true);
   if (d.rows_lds && d.S == 1 && !x->no_sweep && sweep_want) {
     // (a multiple of four waves: a workgroup's waves spread evenly over the four SIMDs, so
     // two or three 4-wave workgroups per CU are resident whenever the occupancy API says so)
     const int64_t wgs = (int64_t)d.RB * d.G + (int64_t)d.RB * d.P;
     int sw = wgs <= x->ncu ? NMC_SWEEP_THREADS / 64 : 4;
-    if (const char* e = getenv("NMC_SWEEP_WAVES")) {
-      const int v = atoi(e);
-      if (v >= 3 && v <= NMC_SWEEP_THREADS / 64) sw = v;
-    }
+    if (const int v = nmc_env_int("NMC_SWEEP_WAVES", 0); v >= 3 && v <= NMC_SWEEP_THREADS / 64)
+      sw = v;
     // a control, a Gibbs and at least one likelihood wave, all resident (in resident batches
     // of chain blocks if need be, with the Gibbs workgroups as their own kernel: nmc_create)
     x->sweep = true;
@@ -191,11 +181,10 @@ static void choose_geometry(nmc_ctx* x) {
     // the count of a publication is the start of the Gibbs workgroups' update, which every
     // step two later waits for -- count it before the control's first tile (cfg-4 shard
     // 30.8 vs 32.4 us/iter, profiles/r04u_ab.txt)
-    d.pubearly = 1;
-    if (const char* e = getenv("NMC_PUB_EARLY")) d.pubearly = atoi(e) != 0;
+    d.pubearly = nmc_env_flag("NMC_PUB_EARLY", true);
     // (the Gibbs workgroups go into their own kernel, Dev.gsep, only when the one grid
     // cannot be resident: nmc_create; NMC_GSEP=1 forces it)
-    if (getenv("NMC_GSEP")) d.gsep = atoi(getenv("NMC_GSEP")) != 0;
+    d.gsep = nmc_env_flag("NMC_GSEP", false);
   }
 }
 
@@ -317,10 +306,7 @@ static int enqueue_prefill(nmc_ctx* x, int a, int b) {
 
 // Diagnostics (NMC_TRACE_CALLS=1): host time of nmc_run's / nmc_synchronize's phases, one
 // line per call on stderr (microseconds since the call's entry).
-static const bool g_trace_calls = [] {
-  const char* e = getenv("NMC_TRACE_CALLS");
-  return e && atoi(e) != 0;
-}();
+static const bool g_trace_calls = nmc_env_flag("NMC_TRACE_CALLS", false);
 struct nmc_call_trace {
   const char* name;
   std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
@@ -342,7 +328,7 @@ struct nmc_call_trace {
 // resident launch's last call ended, fits its variate buffer and finds its variates
 // prefilled there is handed to the running launch as a command (pinned host memory) instead
 // of a new launch: no dispatch, no prologue (rows and chain state stay in LDS), no closing
-// beyond the call's own.  Each call is still closed completely at its end (kernels.h
+// beyond the call's own.  Each call is still closed completely at its end (step.h
 // res_gate): when nmc_synchronize returns, its sample rows, hyper-parameters and state are
 // in HBM exactly as after a launch of that call.  Every other entry point parks the launch
 // first; workgroup 0 parks it by itself after NMC_RESIDENT_IDLE_US (20 ms) without a call.
@@ -511,7 +497,7 @@ static int res_continue(nmc_ctx* x, int i0, int i1) {
   x->cur_slot = (i1 - 1) & 1;
   // the next call's variates beside this one (the same length, while the schedule and the
   // buffer last; NMC_RES_PREFILL=0, diagnostics: none -- the next call then launches anew)
-  static const bool res_prefill_on = !(getenv("NMC_RES_PREFILL") && !atoi(getenv("NMC_RES_PREFILL")));
+  static const bool res_prefill_on = nmc_env_flag("NMC_RES_PREFILL", true);
   if (x->prefill_on && res_prefill_on) {
     const int n1 = std::min({i1 + (i1 - i0), x->n_iter, r.vbase + x->d.vcap});
     if (n1 > i1)
@@ -692,14 +678,14 @@ int nmc_create(nmc_ctx** out, int device, int n_chains, int chain_base, int n_gr
   d.gep = 0;
   d.gpat = 2000000u;
   if (const char* e = getenv("NMC_GSEP_PATIENCE_US")) d.gpat = (unsigned)(atol(e) * 100);
-  x->gserial = getenv("NMC_GSEP_SERIAL") ? atoi(getenv("NMC_GSEP_SERIAL")) : 0;
+  x->gserial = nmc_env_int("NMC_GSEP_SERIAL", 0);
   // nmc_k_fill's grid: 3 blocks of 256 per CU (its Philox instance's 140 VGPRs: three waves
   // per SIMD); NMC_FILL_BPC overrides (A/B)
-  x->fill_bpc = getenv("NMC_FILL_BPC") ? std::max(1, atoi(getenv("NMC_FILL_BPC"))) : 3;
+  x->fill_bpc = std::max(1, nmc_env_int("NMC_FILL_BPC", 3));
   // the pipelined fill beside a step kernel: one block per CU (one wave per SIMD next to the
   // step kernel's), NMC_PREFILL_BPC overrides; NMC_PREFILL=0 turns the pipelining off (A/B)
-  x->prefill_bpc = getenv("NMC_PREFILL_BPC") ? std::max(1, atoi(getenv("NMC_PREFILL_BPC"))) : 1;
-  x->prefill_on = !(getenv("NMC_PREFILL") && atoi(getenv("NMC_PREFILL")) == 0);
+  x->prefill_bpc = std::max(1, nmc_env_int("NMC_PREFILL_BPC", 1));
+  x->prefill_on = nmc_env_flag("NMC_PREFILL", true);
   d.leaf = dleaf;
   d.merge = dmerge;
   HIPCHK(hipMemcpy(dleaf, starts.data(), starts.size() * sizeof(int), hipMemcpyHostToDevice));
@@ -723,10 +709,7 @@ int nmc_create(nmc_ctx** out, int device, int n_chains, int chain_base, int n_gr
       d.S = (int)std::min<int64_t>({64, (nmax + target - 1) / target,
                                     std::max<int64_t>(1, NMC_SPLIT_CU_BASIS / n_groups)});
 #ifdef NMC_DEBUG_KNOBS   // (diagnostic builds only: changes the summation order)
-    if (const char* e = getenv("NMC_SPLIT")) {
-      const int v = atoi(e);
-      if (v >= 1 && v <= 256) d.S = v;
-    }
+    if (const int v = nmc_env_int("NMC_SPLIT", 0); v >= 1 && v <= 256) d.S = v;
 #endif
   }
   d.nmax = (int)((nmax + d.S - 1) / d.S);   // rows of the largest member
@@ -761,8 +744,7 @@ int nmc_create(nmc_ctx** out, int device, int n_chains, int chain_base, int n_gr
   // Measured 1.5-2.5 % slower at cfg 3 than chain-block-major (profiles/r06/r06n_*): off
   d.xpc = 0;
   if (pooling == NMC_POOL_PARTIAL && x->persistent && !x->sweep && d.S == 1 && d.RB <= 8 &&
-      8 % d.RB == 0 && n_groups % (8 / d.RB) == 0 && getenv("NMC_XMAP") &&
-      atoi(getenv("NMC_XMAP")) == 1)
+      8 % d.RB == 0 && n_groups % (8 / d.RB) == 0 && nmc_env_int("NMC_XMAP", 0) == 1)
     d.xpc = 8 / d.RB;
   if (d.S > 1) {   // row split: resident batches of chain blocks, exchange buffers
     NmcCall c;
@@ -774,10 +756,8 @@ int nmc_create(nmc_ctx** out, int device, int n_chains, int chain_base, int n_gr
       return fail(-1, "row split: the S workgroups of one group are not co-resident");
     }
     x->split_batch = (int)std::min<int64_t>(d.RB, c.result / per_cb);
-    if (const char* e = getenv("NMC_SPLIT_BATCH")) {
-      const int v = atoi(e);
-      if (v >= 1 && v < x->split_batch) x->split_batch = v;
-    }
+    if (const int v = nmc_env_int("NMC_SPLIT_BATCH", 0); v >= 1 && v < x->split_batch)
+      x->split_batch = v;
     rc |= dalloc(x, &d.xbuf, (size_t)2 * d.RB * d.G * d.S * x->nacc * 64);
     rc |= dalloc(x, &d.xcnt, (size_t)d.RB * d.G * 32);
     if (rc) { nmc_destroy(x); return rc; }
@@ -786,10 +766,9 @@ int nmc_create(nmc_ctx** out, int device, int n_chains, int chain_base, int n_gr
   // build option NMC_ZIN_BUILD=1: the step kernel draws its {z, log u} itself (a job in
   // each step's tile queue) unless the opt-in one-barrier kernel runs (it DMAs them from
   // the fill's ring); NMC_ZIN=0 keeps the fill (bit-identical; tests compare them)
-  d.zin = NMC_ZIN_BUILD &&
-          !(getenv("NMC_ZIN") && !atoi(getenv("NMC_ZIN")));
+  d.zin = NMC_ZIN_BUILD && nmc_env_flag("NMC_ZIN", true);
   // nmc_k_sweep: every variate drawn in the kernel (NMC_ZIN=1) or from the fill's ring
-  if (x->sweep) d.zin = getenv("NMC_ZIN") ? (atoi(getenv("NMC_ZIN")) != 0) : 0;
+  if (x->sweep) d.zin = nmc_env_flag("NMC_ZIN", false);
   d.thin = 1; d.tune_interval = 100;
   HIPCHK(hipMemcpy(off, group_offsets, (n_groups + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
   if (n_obs > 0)
@@ -1337,10 +1316,9 @@ int nmc_set_resident(nmc_ctx* x, int enable) {
                 : left >= 64 ? 8 : 0;
     if (!r.fill_minb) return 0;
     // (diagnostics, A/B: a smaller fill instance than the one that fits)
-    if (const char* e = getenv("NMC_RES_FILL_MINB")) {
-      const int v = atoi(e);
-      if ((v == 4 || v == 5 || v == 6 || v == 8) && v > r.fill_minb) r.fill_minb = v;
-    }
+    if (const int v = nmc_env_int("NMC_RES_FILL_MINB", 0);
+        (v == 4 || v == 5 || v == 6 || v == 8) && v > r.fill_minb)
+      r.fill_minb = v;
   }
   if (!r.host) {
     const size_t bytes = 512;
@@ -1776,7 +1754,7 @@ int nmc_debug_prior_logpdf(int fam, const double* prm8, const double* xs, int n,
 }
 
 // Diagnostic build only: (re)allocate and zero the stamp buffer (n > 0) and/or copy
-// it back (out != NULL): NMC_STAMP_WORDS uint64 (kernels.h NMC_STAMP / NMC_CS layouts).
+// it back (out != NULL): NMC_STAMP_WORDS uint64 (stamps.h NMC_STAMP / NMC_CS layouts).
 int nmc_debug_stamps(nmc_ctx* x, int n, uint64_t* out) {
   RES_PARK(x);
 #if defined(NMC_STAMPS) || defined(NMC_CSTAMPS)
@@ -1786,7 +1764,7 @@ int nmc_debug_stamps(nmc_ctx* x, int n, uint64_t* out) {
       if (int rc = dalloc(x, &x->d.stamps, NMC_STAMP_WORDS)) return rc;
     HIPCHK(hipMemset(x->d.stamps, 0, NMC_STAMP_WORDS * 8));
   }
-  if (out) {   // layouts: kernels.h NMC_STAMP / NMC_CS (nmc_k_run), sweep.h NMC_RS_STAMP
+  if (out) {   // layouts: stamps.h NMC_STAMP / NMC_CS (nmc_k_run), sweep.h NMC_RS_STAMP
     HIPCHK(hipStreamSynchronize(x->stream));
     HIPCHK(hipMemcpy(out, x->d.stamps, NMC_STAMP_WORDS * 8, hipMemcpyDeviceToHost));
   }

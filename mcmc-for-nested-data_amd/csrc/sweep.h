@@ -2,7 +2,7 @@
 // no row split, in three waves per SIMD.
 //
 // Same work, tile partition, summation orders, variates and outputs as nmc_k_run
-// (kernels.h) -- the two are bit-identical and the tests compare them -- built around what
+// (step.h) -- the two are bit-identical and the tests compare them -- built around what
 // MI355X measurements say bounds the loop (profiles/r04_fp64issue.jsonl): one wave issues an
 // fp64 VALU instruction at most every ~5.8 cycles, two waves on a SIMD every ~4.7, three
 // every ~4.5 (the paired row loop with its LDS reads: 7.0 / 5.3 / 4.9).  nmc_k_run's eight
@@ -19,7 +19,7 @@
 //   * {hyper z, Gamma((G-1)/2)} of a Gibbs task (HyperParameter.update :481-498): drawn by
 //     the Gibbs wave for its own task.
 //
-// MODE (kernels.h NMC_MODE_*):
+// MODE (step.h NMC_MODE_*):
 //   NOPOOL    none / complete pooling, 64 chains per workgroup
 //   HALF      none / complete pooling, 32 chains per workgroup (lanes l, l + 32: one chain)
 //   SYNC_REG  partial pooling, G <= 64: the Gibbs wave fetches a task's G published values
@@ -751,7 +751,7 @@ nmc_k_sweep(nmc_sweep_args<Fam> a_arg) {
         for (int q = 0; q < MP; ++q)
           if (q == p) thp[q] = prop;
         const typename Fam::Reg reg = fam.prepare(thp);
-        // quad rows ({x, y}, kernels.h nmc_ll_rows_lds_quad): intercept and slope of the four
+        // quad rows ({x, y}, rows.h nmc_ll_rows_lds_quad): intercept and slope of the four
         // chains of this lane's quarter position
         const bool quad = Fam::ASM_ROWS && !HALF && d.quad;
         double q4c[4], q4d[4];

@@ -65,8 +65,8 @@ static int nmc_sweep_call_t(nmc_ctx* x, const Fam& fam, NmcCall& c) {
       });
     }
     case NMC_OP_CAN_PERSIST: {   // may every workgroup of the grid be resident at once?
-      if (const char* e = getenv("NMC_PERSIST")) {
-        c.result = atoi(e) != 0;
+      if (const int f = nmc_env_persist(); f >= 0) {
+        c.result = f;
         return 0;
       }
       int nb = 0;

@@ -142,7 +142,6 @@ extern "C" int nmc_user_family_compile(const char* source, int n_fields, int n_p
   // the library's own build-time kernel constants, so the JIT kernels index LDS and tiles
   // exactly as the host carve (nmc_lds / nmc_tiles) computed them
   const std::string defs = "#define NMC_NSLOT_N " + std::to_string((int)NMC_NSLOT) +
-                           "\n#define NMC_HYPER_NS " + std::to_string((int)NMC_HYPER_NS) +
                            "\n#define NMC_LDS_ROW_DOUBLES " +
                            std::to_string((int)NMC_LDS_ROW_DOUBLES) +
                            "\n#define NMC_RUN_THREADS " + std::to_string((int)NMC_RUN_THREADS) +
@@ -211,8 +210,8 @@ int nmc_call_user(nmc_ctx* x, NmcCall& c) {
       return rc ? rc : e;
     }
     case NMC_OP_CAN_PERSIST: {
-      if (const char* e = getenv("NMC_PERSIST")) {
-        c.result = atoi(e) != 0;
+      if (const int f = nmc_env_persist(); f >= 0) {
+        c.result = f;
         return 0;
       }
       int nb = 0;

@@ -27,10 +27,10 @@ NCU = 256                                    # CUs of an MI355X (the half-layout
 
 
 # ---------------------------------------------------------------------------------------
-# path arithmetic (csrc/kernels.h nmc_row_block, nmc_lds; csrc/nestmc.hip)
+# path arithmetic (csrc/rows.h nmc_row_block, csrc/dev.h nmc_lds; csrc/nestmc.hip)
 # ---------------------------------------------------------------------------------------
 def row_block(nf):
-    """kernels.h nmc_row_block: rows per block of the scalar-load / staged loops."""
+    """rows.h nmc_row_block: rows per block of the scalar-load / staged loops."""
     if nf <= 4:
         return 16 // nf
     return 4 if 32 // nf >= 4 else max(32 // nf, 1)
@@ -46,7 +46,7 @@ def pairwise_leaves(G):
 
 
 def carve_columns(nacc, P, partial, G):
-    """kernels.h nmc_lds without the rows and without a Gibbs payload: 512-byte columns."""
+    """dev.h nmc_lds without the rows and without a Gibbs payload: 512-byte columns."""
     leaves = pairwise_leaves(G)
     ntail = max(m - (m - m % 8 if m >= 8 else 0) for m in leaves)
     cols = P + nacc * 16 + 5 * P + 4 + 8 + 1
@@ -358,7 +358,7 @@ class FastNested:
 # can reproduce exactly (y-only regression rows, sigma = 1: e = b0 - y, acc = fma(e, e, acc))
 # ---------------------------------------------------------------------------------------
 def tiles(n, tile=64, nslot=16):
-    """kernels.h nmc_tiles: [(start, rows)] of a group of n rows."""
+    """dev.h nmc_tiles: [(start, rows)] of a group of n rows."""
     if n <= 0:
         return []
     t = min(-(-n // tile), nslot)

@@ -193,7 +193,7 @@ def test_eval_group_ll_matches_oracle(gpu_lib):
 ])
 def test_paired_rows_bit_identical(gpu_lib, kind, C, G, N, ragged, n_iter):
     """The paired-chain row loop (each lane evaluates its row pair half for its own chain
-    and for lane ^ 32's, kernels.h nmc_ll_rows_lds<Fam, true>) and, for {x, y} rows, the
+    and for lane ^ 32's, rows.h nmc_ll_rows_lds<Fam, true>) and, for {x, y} rows, the
     quad-chain loop (each lane evaluates rows 4m+q for the four chains of its quarter
     position, nmc_ll_rows_lds_quad; the default) reproduce the one-chain broadcast loop bit
     for bit: flags, proposal LLs and recorded rows; so does the 64-chain layout where none

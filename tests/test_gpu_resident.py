@@ -1,7 +1,7 @@
 """GPU: the resident step launch (nmc_set_resident) changes no bit.
 
 One launch serves consecutive nmc_run calls: a call continuing where the last one ended is
-handed to the running launch (kernels.h res_gate) instead of a new launch, and every other
+handed to the running launch (step.h res_gate) instead of a new launch, and every other
 entry point parks it.  Each call is closed as a launch ends, so every call plan below --
 synchronized calls, calls queued without a synchronize, an idle gap longer than the
 launch's own park, a state read (park) in the middle, explicit prefills, a call that does

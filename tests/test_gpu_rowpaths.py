@@ -11,7 +11,7 @@ and every test asserts from Engine.launch_config() that its shape took the path 
 2. test_step_equals_group_kernel: after a short run the step kernel's stored group LLs are
    eval_group_ll of its stored values BIT FOR BIT -- the quad / paired / broadcast LDS
    loops, the scalar-load loop and the staged loop against the group kernel's summation of
-   the same rows (kernels.h: "a chain's stored group LL never depends on which kernel
+   the same rows (ll_kernels.h: "a chain's stored group LL never depends on which kernel
    produced it") -- and the variants of a path (NMC_ROWS, NMC_HALF,
    NMC_PERSIST) agree with each other bit for bit.
 3. test_chain_matches_oracle: oracle chain parity on the paths that never had one.
@@ -39,7 +39,7 @@ What the matrix found: nmc_ll_rows_staged clamped its LDS-DMA reads at the last 
 16 bytes wholly inside the group, so a group ENDING on an odd double offset (odd n_fields x
 an odd row count before its end) lost its last double -- the y of its last row -- and summed
 a stale value instead.  Every staged case with odd n_fields failed tests 2 and 3 until the
-clamp moved to the 16 bytes that hold the last double (kernels.h).
+clamp moved to the 16 bytes that hold the last double (rows.h nmc_ll_rows_staged).
 """
 
 import contextlib

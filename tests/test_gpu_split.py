@@ -3,7 +3,7 @@ posteriorSampling.py:662-685 -- every observation in ONE group, so one (chain, g
 is a single workgroup's worth of chains over the whole dataset).
 
 Groups much larger than one workgroup's 64 KiB LDS row area are shared by S member
-workgroups (kernels.h nmc_split_exchange): each owns a contiguous row chunk, the
+workgroups (gibbs.h nmc_split_exchange): each owns a contiguous row chunk, the
 members exchange their partial sums every step and all make the same decision.
 
 * complete pooling at n_total = 120 000 rows and none pooling with four 20 000-row

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Where a cfg-3 parameter step's time goes (diagnostics): nmc_k_run's control-path stamps
-(kernels.h NMC_CS) of workgroup 0 in the diagnostic build.
+(stamps.h NMC_CS) of workgroup 0 in the diagnostic build.
 
     make -C mcmc-for-nested-data_amd/csrc cstamps
     python tools/cstamps.py [WORKLOAD] [K]
