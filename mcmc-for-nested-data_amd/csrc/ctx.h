@@ -139,23 +139,26 @@ static inline size_t lds_bytes_for(const nmc_ctx* x, int hlds, int rows_lds) {
                                   : (x->nf <= 4 ? 0 : nmc_stage_doubles(x->nf, d.W)))
              .total * 512;
 }
+// mode of the persistent partial-pooling kernel (what its occupancy query asks about): the
+// sweep (x->sweep, nestmc.hip choose_geometry) or nmc_k_run by its Gibbs hand-off
+static inline int nmc_persist_mode(const nmc_ctx* x) {
+  if (x->sweep) return NMC_MODE_SYNC_OWN;
+  return x->d.hreg ? NMC_MODE_SYNC_REG : x->d.hlds ? NMC_MODE_SYNC_LDS : NMC_MODE_SYNC;
+}
+// mode of the step kernel that runs (nestmc.hip choose_kernel has settled x->persistent)
 static inline int run_mode(const nmc_ctx* x) {
   if (x->pooling != NMC_POOL_PARTIAL) return x->d.CL == 32 ? NMC_MODE_HALF : NMC_MODE_NOPOOL;
-  if (x->sweep)
-    return x->d.G <= 64 ? NMC_MODE_SYNC_REG : x->d.G <= 128 ? NMC_MODE_SYNC_LDS : NMC_MODE_SYNC_OWN;
+  if (x->sweep) return NMC_MODE_SYNC_OWN;
   if (!x->persistent) return NMC_MODE_LAUNCH;
-  if (x->d.hreg) return NMC_MODE_SYNC_REG;
-  return x->d.hlds ? NMC_MODE_SYNC_LDS : NMC_MODE_SYNC;
+  return nmc_persist_mode(x);
 }
 
-// LDS of nmc_k_sweep (sweep.h); partial pooling over G > 128 groups also runs the Gibbs
-// workgroups (SYNC_OWN) in the same launch: their hyper carve (nmc_lds, no rows) must fit
+// LDS of nmc_k_sweep (sweep.h); unless the Gibbs workgroups are their own kernel (Dev.gsep)
+// they run in the same launch: their hyper carve (nmc_lds, no rows) must fit
 static inline size_t sweep_lds_bytes(const nmc_ctx* x) {
   const Dev& d = x->d;
-  const bool partial = x->pooling == NMC_POOL_PARTIAL;
-  size_t b = (size_t)nmc_sweep_lds(x->nacc, d.P, partial, d.G > 64 && d.G <= 128 ? 1 : 0, d.G,
-                                   d.nmax * x->nf).total * 512;
-  if (partial && d.G > 128 && !d.gsep)
+  size_t b = (size_t)nmc_sweep_lds(x->nacc, d.P, d.nmax * x->nf).total * 512;
+  if (!d.gsep)
     b = std::max(b, (size_t)nmc_lds(0, d.P, 1, d.nleaf, d.ntail, d.W, d.G, 0, 0).total * 512);
   return b;
 }
@@ -167,13 +170,18 @@ static inline size_t sweep_gibbs_lds_bytes(const nmc_ctx* x) {
 // workgroups of the sweep grid: RB * G likelihood workgroups (+ RB * P Gibbs workgroups)
 static inline int64_t sweep_grid(const nmc_ctx* x) {
   const Dev& d = x->d;
-  return (int64_t)d.RB * d.G +
-         (x->pooling == NMC_POOL_PARTIAL && d.G > 128 && !d.gsep ? (int64_t)d.RB * d.P : 0);
+  return (int64_t)d.RB * d.G + (!d.gsep ? (int64_t)d.RB * d.P : 0);
 }
 
-static inline size_t run_lds_bytes(const nmc_ctx* x) {
+// LDS of the persistent partial-pooling kernel (its occupancy query), and of the step kernel
+// that runs (launch per iteration: no Gibbs payload)
+static inline size_t nmc_persist_lds(const nmc_ctx* x) {
   if (x->sweep) return sweep_lds_bytes(x);
-  return lds_bytes_for(x, x->persistent && x->d.hlds ? 1 : 0, x->d.rows_lds);
+  return lds_bytes_for(x, x->d.hlds, x->d.rows_lds);
+}
+static inline size_t run_lds_bytes(const nmc_ctx* x) {
+  if (x->sweep || x->persistent) return nmc_persist_lds(x);
+  return lds_bytes_for(x, 0, x->d.rows_lds);
 }
 
 // Resident blocks per CU to rely on, from the occupancy API's answer nb.  The API can
@@ -185,15 +193,14 @@ static inline int nmc_safe_blocks(const nmc_ctx* x, int nb) {
   const int W = x->d.W;
   return W % 4 == 0 ? std::min(nb, 24 / W) : (nb > 1 ? nb - 1 : nb);
 }
-// mode of the persistent partial-pooling kernel (its occupancy query)
-static inline int nmc_persist_mode(const nmc_ctx* x) {
-  if (x->sweep) return run_mode(x);
-  return x->d.hreg ? NMC_MODE_SYNC_REG : x->d.hlds ? NMC_MODE_SYNC_LDS : NMC_MODE_SYNC;
-}
-// LDS of the persistent partial-pooling kernel (its occupancy query)
-static inline size_t nmc_persist_lds(const nmc_ctx* x) {
-  if (x->sweep) return sweep_lds_bytes(x);
-  return lds_bytes_for(x, x->d.hlds && !x->d.hreg, x->d.rows_lds);
+// Resident workgroups of kernel k at 64 * W threads and lds bytes of dynamic LDS, on the
+// whole device: the occupancy API's blocks per CU, cut to nmc_safe_blocks, times the CUs.
+// -1: no such kernel, or the query failed.
+static inline int64_t nmc_resident_wgs(const nmc_ctx* x, const void* k, size_t lds) {
+  int nb = 0;
+  if (!k || hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, 64 * x->d.W, lds) != hipSuccess)
+    return -1;
+  return (int64_t)nmc_safe_blocks(x, nb) * x->ncu;
 }
 
 // dynamic LDS of nmc_k_group_part: the tile slots and (rows in LDS) the member's rows

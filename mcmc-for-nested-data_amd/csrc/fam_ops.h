@@ -59,12 +59,8 @@ static int nmc_launch_run(nmc_ctx* x, const Fam& fam, int i0, int i1, int flags,
 template <class Fam>
 static bool nmc_can_persist(nmc_ctx* x) {
   if (const int f = nmc_env_persist(); f >= 0) return f != 0;
-  int nb = 0;
   const void* k = nmc_run_kernel<Fam>(x, nmc_persist_mode(x));
-  if (!k || hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, 64 * x->d.W,
-                                                         nmc_persist_lds(x)) != hipSuccess)
-    return false;
-  return (int64_t)x->d.RB * x->d.G * x->d.S <= (int64_t)nmc_safe_blocks(x, nb) * x->ncu;
+  return (int64_t)x->d.RB * x->d.G * x->d.S <= nmc_resident_wgs(x, k, nmc_persist_lds(x));
 }
 
 template <class Fam>
@@ -77,22 +73,15 @@ static int nmc_fam_call(nmc_ctx* x, const Fam& fam, NmcCall& c) {
       return 0;
     case NMC_OP_RES_OK: {   // a resident instance of the run mode, its whole grid co-resident
       const void* k = x->d.rows_lds ? nmc_run_kernel_res<Fam>(run_mode(x)) : nullptr;
-      int nb = 0;
-      c.result = 0;
-      if (k && hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, 64 * x->d.W,
-                                                            run_lds_bytes(x)) == hipSuccess)
-        c.result = (int64_t)x->d.RB * x->d.G * x->d.S <= (int64_t)nmc_safe_blocks(x, nb) * x->ncu;
+      c.result = (int64_t)x->d.RB * x->d.G * x->d.S <= nmc_resident_wgs(x, k, run_lds_bytes(x));
       hipFuncAttributes fa{};
       c.result2 = k && hipFuncGetAttributes(&fa, k) == hipSuccess ? fa.numRegs : 0;   // VGPRs
       return 0;
     }
     case NMC_OP_CAPACITY: {   // resident step-kernel workgroups of the run mode (safe count)
-      int nb = 0;
-      const void* k = nmc_run_kernel<Fam>(x, run_mode(x));
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, 64 * x->d.W, run_lds_bytes(x)) !=
-          hipSuccess)
-        return nmc_fail(-2, "occupancy query failed");
-      c.result = nmc_safe_blocks(x, nb) * x->ncu;
+      const int64_t n = nmc_resident_wgs(x, nmc_run_kernel<Fam>(x, run_mode(x)), run_lds_bytes(x));
+      if (n < 0) return nmc_fail(-2, "occupancy query failed");
+      c.result = (int)n;
       return 0;
     }
     case NMC_OP_GROUP_LL: {   // c.aux: [S][NACC][G][C] member partials

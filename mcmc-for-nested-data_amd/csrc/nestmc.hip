@@ -175,7 +175,7 @@ static void choose_geometry(nmc_ctx* x) {
     if (const int v = nmc_env_int("NMC_SWEEP_WAVES", 0); v >= 3 && v <= NMC_SWEEP_THREADS / 64)
       sw = v;
     // a control, a Gibbs and at least one likelihood wave, all resident (in resident batches
-    // of chain blocks if need be, with the Gibbs workgroups as their own kernel: nmc_create)
+    // of chain blocks if need be, with the Gibbs workgroups as their own kernel: choose_kernel)
     x->sweep = true;
     d.W = sw;
     // the count of a publication is the start of the Gibbs workgroups' update, which every
@@ -183,9 +183,69 @@ static void choose_geometry(nmc_ctx* x) {
     // 30.8 vs 32.4 us/iter, profiles/r04u_ab.txt)
     d.pubearly = nmc_env_flag("NMC_PUB_EARLY", true);
     // (the Gibbs workgroups go into their own kernel, Dev.gsep, only when the one grid
-    // cannot be resident: nmc_create; NMC_GSEP=1 forces it)
+    // cannot be resident: choose_kernel; NMC_GSEP=1 forces it)
     d.gsep = nmc_env_flag("NMC_GSEP", false);
   }
+}
+
+// Which step kernel runs the geometry choose_geometry picked, and how: the sweep (one grid,
+// or beside its Gibbs kernel in resident batches of chain blocks), nmc_k_run persistent or
+// launched per iteration, the row split's resident batches with their exchange buffers, and
+// where the variates are drawn.  Everything run_mode() and nmc_launch_config() report is
+// settled when this returns.
+static int choose_kernel(nmc_ctx* x) {
+  Dev& d = x->d;
+  if (run_lds_bytes(x) > (size_t)160 * 1024)
+    return fail(-1, "workgroup state exceeds the 160 KiB LDS of a CU (too many parameters, "
+                    "groups or rows per group)");
+  if (x->pooling == NMC_POOL_PARTIAL) {
+    NmcCall c;
+    c.op = NMC_OP_CAN_PERSIST;
+    if (int rc = nmc_call_family(x, c)) return rc;
+    if (x->sweep && c.result != 1 && !d.gsep && !getenv("NMC_GSEP")) {
+      // the likelihood and Gibbs workgroups in one grid do not fit: two kernels, one per
+      // stream (nmc_k_sweep + nmc_k_sweep_gibbs), each workgroup with its own LDS size
+      d.gsep = 1;
+      if (int rc = nmc_call_family(x, c)) return rc;
+    }
+    if (x->sweep && c.result != 1) {   // the sweep grid cannot be resident: nmc_k_run
+      x->no_sweep = true;
+      choose_geometry(x);
+      if (int rc = nmc_call_family(x, c)) return rc;
+    }
+    // row split: always persistent (the members exchange every step), in resident batches
+    // of chain blocks when the whole grid is not (chain blocks are independent)
+    x->persistent = c.result == 1 || d.S > 1;
+  }
+  // XCD-aware placement of nmc_k_run's persistent partial-pooling grid (Dev.xpc, NMC_XMAP=1):
+  // the RB chain blocks on 8 / RB XCDs each, when RB divides 8 and the groups split evenly.
+  // Measured 1.5-2.5 % slower at cfg 3 than chain-block-major (profiles/r06/r06n_*): off
+  d.xpc = 0;
+  if (x->pooling == NMC_POOL_PARTIAL && x->persistent && !x->sweep && d.S == 1 && d.RB <= 8 &&
+      8 % d.RB == 0 && x->G % (8 / d.RB) == 0 && nmc_env_int("NMC_XMAP", 0) == 1)
+    d.xpc = 8 / d.RB;
+  if (d.S > 1) {   // row split: resident batches of chain blocks, exchange buffers
+    NmcCall c;
+    c.op = NMC_OP_CAPACITY;
+    if (int rc = nmc_call_family(x, c)) return rc;
+    const int64_t per_cb = (int64_t)d.G * d.S;
+    if (c.result < per_cb)
+      return fail(-1, "row split: the S workgroups of one group are not co-resident");
+    x->split_batch = (int)std::min<int64_t>(d.RB, c.result / per_cb);
+    if (const int v = nmc_env_int("NMC_SPLIT_BATCH", 0); v >= 1 && v < x->split_batch)
+      x->split_batch = v;
+    int rc = dalloc(x, &d.xbuf, (size_t)2 * d.RB * d.G * d.S * x->nacc * 64);
+    rc |= dalloc(x, &d.xcnt, (size_t)d.RB * d.G * 32);
+    if (rc) return rc;
+    HIPCHK(hipMemset(d.xcnt, 0, (size_t)d.RB * d.G * 32 * sizeof(unsigned)));
+  }
+  // build option NMC_ZIN_BUILD=1: the step kernel draws its {z, log u} itself (a job in
+  // each step's tile queue) unless the opt-in one-barrier kernel runs (it DMAs them from
+  // the fill's ring); NMC_ZIN=0 keeps the fill (bit-identical; tests compare them)
+  d.zin = NMC_ZIN_BUILD && nmc_env_flag("NMC_ZIN", true);
+  // nmc_k_sweep: every variate drawn in the kernel (NMC_ZIN=1) or from the fill's ring
+  if (x->sweep) d.zin = nmc_env_flag("NMC_ZIN", false);
+  return 0;
 }
 
 // numpy's pairwise-sum recursion over G groups (numpy/_core/src/umath/loops_utils.h):
@@ -520,6 +580,177 @@ int nmc_device_count(int* n) {
   return 0;
 }
 
+// nmc_create after validation, on the context's device: streams and events, device memory,
+// the numpy pairwise plan, the row split, the geometry and the step kernel, the initial state.
+// A failure returns its code; nmc_create destroys the half-built context once.
+static int create_on_device(nmc_ctx* x, const int64_t* group_offsets, const double* obs,
+                            const int* prior_family, const double* prior_params) {
+  const int device = x->device, n_chains = x->C, chain_base = x->chain_base, n_groups = x->G,
+            n_params = x->P, pooling = x->pooling, ll_family = x->family, n_fields = x->nf,
+            rng_mode = x->rng, n_ll_consts = (int)x->llc.size();
+  const uint32_t seed = x->seed;
+  const int64_t n_obs = x->n_obs;
+  const double* ll_consts = x->llc.data();
+  hipError_t e = hipStreamCreateWithFlags(&x->stream, hipStreamNonBlocking);
+  if (e != hipSuccess) return fail(-2, std::string("hipStreamCreate: ") + hipGetErrorString(e));
+  for (auto& ev : x->ev) hipEventCreate(&ev);
+  e = hipStreamCreateWithFlags(&x->gstream, hipStreamNonBlocking);
+  if (e != hipSuccess) return fail(-2, std::string("hipStreamCreate: ") + hipGetErrorString(e));
+  for (auto& ev : x->gev) hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+  e = hipStreamCreateWithFlags(&x->pstream, hipStreamNonBlocking);
+  if (e != hipSuccess) return fail(-2, std::string("hipStreamCreate: ") + hipGetErrorString(e));
+  hipEventCreateWithFlags(&x->pf_ev, hipEventDisableTiming);
+  for (auto& ev : x->rd_ev) {   // (recorded on the empty stream: complete)
+    hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+    hipEventRecord(ev, x->stream);
+  }
+
+  Dev& d = x->d;
+  const size_t PGC = (size_t)n_params * n_groups * n_chains, GC = (size_t)n_groups * n_chains,
+               PC = (size_t)n_params * n_chains;
+  int rc = 0;
+  int64_t* off = nullptr;
+  double* dobs = nullptr;
+  int* pf = nullptr;
+  double* pp = nullptr;
+  rc |= dalloc(x, &off, n_groups + 1);
+  rc |= dalloc(x, &dobs, (size_t)n_obs * n_fields + 4);   // (+32 B: staged-row DMA slack)
+  rc |= dalloc(x, &pf, n_params);
+  rc |= dalloc(x, &pp, (size_t)8 * n_params);
+  // (+72 C + 128 slack: the Gibbs wave reads 72 groups' values unconditionally, and the
+  // payload copies read whole 64-chain rows of the last group)
+  rc |= dalloc(x, &d.vb0, PGC + (size_t)72 * n_chains + 128);
+  rc |= dalloc(x, &d.vb1, PGC + (size_t)72 * n_chains + 128);
+  rc |= dalloc(x, &d.lp, PGC);
+  rc |= dalloc(x, &d.ll, GC);
+  rc |= dalloc(x, &d.scale, PGC);
+  rc |= dalloc(x, &d.nacc, PGC);
+  rc |= dalloc(x, &d.nrej, PGC);
+  rc |= dalloc(x, &d.tacc, PGC);
+  // hyper-parameters after iteration t live in slot t & 1 ([2][P][C]), like the values
+  rc |= dalloc(x, &d.mu, 2 * PC);
+  rc |= dalloc(x, &d.s2, 2 * PC);
+  rc |= dalloc(x, &d.hsd, 2 * PC);
+  rc |= dalloc(x, &d.hlsd, 2 * PC);
+  if (rc) return rc;
+  d.off = off; d.obs = dobs; d.pfam = pf; d.ppar = pp;
+  d.C = n_chains; d.G = n_groups; d.P = n_params; d.pooling = pooling; d.nf = n_fields;
+  d.chain_base = chain_base; d.rng_mode = rng_mode; d.seed = seed;
+  d.CB = (n_chains + 63) / 64;
+  d.ha = (n_groups - 1) / 2.0;
+  d.hlga = lgamma(d.ha > 0 ? d.ha : 1.0);
+  {
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0)
+      x->ncu = prop.multiProcessorCount;
+  }
+  x->nacc = ll_family == NMC_LL_GAUSS_MEAN ? n_fields : 1;
+  if (ll_family >= NMC_LL_USER_BASE) {   // runtime-compiled family: module + constants
+    if (int rc0 = nmc_user_attach(x, ll_family)) return rc0;
+    if (n_ll_consts > 0) {
+      if (int rc0 = dalloc(x, &x->user_k, (size_t)n_ll_consts)) return rc0;
+      HIPCHK(hipMemcpy(x->user_k, ll_consts, (size_t)n_ll_consts * 8, hipMemcpyHostToDevice));
+    }
+  }
+  // numpy pairwise-sum plan of the hyper update (partial pooling)
+  std::vector<int> starts, merges;
+  pairwise_plan(0, n_groups, starts, merges);
+  int ntail = 0;
+  for (size_t k = 0; k < starts.size(); ++k) {
+    const int m = (k + 1 < starts.size() ? starts[k + 1] : n_groups) - starts[k];
+    const int m8 = m >= 8 ? m - m % 8 : 0;
+    ntail = std::max(ntail, m - m8);
+  }
+  starts.push_back(n_groups);
+  d.nleaf = (int)starts.size() - 1;
+  d.nmerge = (int)merges.size() / 2;
+  d.ntail = ntail;
+  int* dleaf = nullptr;
+  int* dmerge = nullptr;
+  rc |= dalloc(x, &dleaf, starts.size());
+  rc |= dalloc(x, &dmerge, merges.size());
+  // [RB][P][8 shards][32], RB <= ceil(C / 32)
+  rc |= dalloc(x, &d.cnt, cnt_bytes(x) / sizeof(unsigned));
+  rc |= dalloc(x, &d.hrd, hrd_words(x));
+  // Dev.gsep role words [RB <= ceil(C / 32)][16] and the fallback count
+  rc |= dalloc(x, &d.grole, grole_words(x));
+  rc |= dalloc(x, &d.gfb, 32);
+  if (rc) return rc;
+  {
+    void* h = nullptr;
+    void* dp = nullptr;
+    e = hipHostMalloc(&h, 64, hipHostMallocCoherent | hipHostMallocMapped);
+    if (e == hipSuccess) x->tmo_host = (volatile unsigned*)h;
+    if (e == hipSuccess) e = hipHostGetDevicePointer(&dp, h, 0);
+    if (e != hipSuccess)
+      return fail(-2, std::string("timeout word (pinned host memory): ") + hipGetErrorString(e));
+    memset(h, 0, 64);
+    d.tmo = (unsigned*)dp;
+  }
+  HIPCHK(hipMemset(d.cnt, 0, cnt_bytes(x)));
+  HIPCHK(hipMemset(d.hrd, 0, hrd_words(x) * sizeof(unsigned)));
+  HIPCHK(hipMemset(d.grole, 0, grole_words(x) * sizeof(unsigned long long)));
+  HIPCHK(hipMemset(d.gfb, 0, 32 * sizeof(unsigned)));
+  d.pbase = d.xbase = 0;
+  // Dev.gsep: how long the two kernels may take to meet before the likelihood workgroups take
+  // a launch's Gibbs tasks over (NMC_GSEP_PATIENCE_US, default 20 ms: 2 ms was sometimes too
+  // short for the Gibbs kernel to be dispatched beside a running step kernel and the variate
+  // fill, and a launch fell back while both kernels ran -- the same results, slower);
+  // NMC_GSEP_SERIAL (tests) serializes them on one stream
+  d.gep = 0;
+  d.gpat = 2000000u;
+  if (const char* e = getenv("NMC_GSEP_PATIENCE_US")) d.gpat = (unsigned)(atol(e) * 100);
+  x->gserial = nmc_env_int("NMC_GSEP_SERIAL", 0);
+  // nmc_k_fill's grid: 3 blocks of 256 per CU (its Philox instance's 140 VGPRs: three waves
+  // per SIMD); NMC_FILL_BPC overrides (A/B)
+  x->fill_bpc = std::max(1, nmc_env_int("NMC_FILL_BPC", 3));
+  // the pipelined fill beside a step kernel: one block per CU (one wave per SIMD next to the
+  // step kernel's), NMC_PREFILL_BPC overrides; NMC_PREFILL=0 turns the pipelining off (A/B)
+  x->prefill_bpc = std::max(1, nmc_env_int("NMC_PREFILL_BPC", 1));
+  x->prefill_on = nmc_env_flag("NMC_PREFILL", true);
+  d.leaf = dleaf;
+  d.merge = dmerge;
+  HIPCHK(hipMemcpy(dleaf, starts.data(), starts.size() * sizeof(int), hipMemcpyHostToDevice));
+  if (!merges.empty())
+    HIPCHK(hipMemcpy(dmerge, merges.data(), merges.size() * sizeof(int), hipMemcpyHostToDevice));
+  int64_t nmax = 0;
+  for (int g = 0; g < n_groups; ++g)
+    nmax = std::max<int64_t>(nmax, group_offsets[g + 1] - group_offsets[g]);
+  x->nmax_group = nmax;
+  // Row split: groups far larger than one workgroup's 64 KiB LDS row area are shared by S
+  // workgroups, at most 64 and at most one per CU of a full MI355X (256 CUs) per group.
+  // S depends on (rows, fields, groups) only -- never on the chain count or on the
+  // device's CU count -- so the partial-sum order, and every result, is the same whatever
+  // the sharding, the launch batching or the GPU partition (a partition too small to
+  // hold the S members of one group at once refuses the run: choose_kernel).
+  d.S = 1;
+  d.cb0 = 0;
+  {
+    const int64_t target = std::max<int64_t>(256, (64 * 1024) / (n_fields * 8));
+    if (nmax > 2 * target)
+      d.S = (int)std::min<int64_t>({64, (nmax + target - 1) / target,
+                                    std::max<int64_t>(1, NMC_SPLIT_CU_BASIS / n_groups)});
+#ifdef NMC_DEBUG_KNOBS   // (diagnostic builds only: changes the summation order)
+    if (const int v = nmc_env_int("NMC_SPLIT", 0); v >= 1 && v <= 256) d.S = v;
+#endif
+  }
+  d.nmax = (int)((nmax + d.S - 1) / d.S);   // rows of the largest member
+  choose_geometry(x);
+  if (int rc2 = choose_kernel(x)) return rc2;
+  d.thin = 1; d.tune_interval = 100;
+  HIPCHK(hipMemcpy(off, group_offsets, (n_groups + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
+  if (n_obs > 0)
+    HIPCHK(hipMemcpy(dobs, obs, (size_t)n_obs * n_fields * sizeof(double), hipMemcpyHostToDevice));
+  if (prior_family) HIPCHK(hipMemcpy(pf, prior_family, n_params * sizeof(int), hipMemcpyHostToDevice));
+  if (prior_params) HIPCHK(hipMemcpy(pp, prior_params, 8 * n_params * sizeof(double), hipMemcpyHostToDevice));
+  HIPCHK(hipMemset(d.nacc, 0, PGC * sizeof(int)));
+  HIPCHK(hipMemset(d.nrej, 0, PGC * sizeof(int)));
+  HIPCHK(hipMemset(d.tacc, 0, PGC * sizeof(long long)));
+  std::vector<double> ones(PGC, 1.0);
+  HIPCHK(hipMemcpy(d.scale, ones.data(), PGC * sizeof(double), hipMemcpyHostToDevice));
+  return 0;
+}
+
 int nmc_create(nmc_ctx** out, int device, int n_chains, int chain_base, int n_groups,
                int n_params, int pooling, int ll_family, const double* ll_consts,
                int n_ll_consts, const int64_t* group_offsets, const double* obs,
@@ -567,219 +798,11 @@ int nmc_create(nmc_ctx** out, int device, int n_chains, int chain_base, int n_gr
   x->llc.assign(ll_consts, ll_consts + n_ll_consts);
   hipError_t e = hipSetDevice(device);
   if (e != hipSuccess) { delete x; return fail(-2, std::string("hipSetDevice: ") + hipGetErrorString(e)); }
-  e = hipStreamCreateWithFlags(&x->stream, hipStreamNonBlocking);
-  if (e != hipSuccess) { nmc_destroy(x); return fail(-2, std::string("hipStreamCreate: ") + hipGetErrorString(e)); }
-  for (auto& ev : x->ev) hipEventCreate(&ev);
-  e = hipStreamCreateWithFlags(&x->gstream, hipStreamNonBlocking);
-  if (e != hipSuccess) { nmc_destroy(x); return fail(-2, std::string("hipStreamCreate: ") + hipGetErrorString(e)); }
-  for (auto& ev : x->gev) hipEventCreateWithFlags(&ev, hipEventDisableTiming);
-  e = hipStreamCreateWithFlags(&x->pstream, hipStreamNonBlocking);
-  if (e != hipSuccess) { nmc_destroy(x); return fail(-2, std::string("hipStreamCreate: ") + hipGetErrorString(e)); }
-  hipEventCreateWithFlags(&x->pf_ev, hipEventDisableTiming);
-  for (auto& ev : x->rd_ev) {   // (recorded on the empty stream: complete)
-    hipEventCreateWithFlags(&ev, hipEventDisableTiming);
-    hipEventRecord(ev, x->stream);
-  }
-
-  Dev& d = x->d;
-  const size_t PGC = (size_t)n_params * n_groups * n_chains, GC = (size_t)n_groups * n_chains,
-               PC = (size_t)n_params * n_chains;
-  int rc = 0;
-  int64_t* off = nullptr;
-  double* dobs = nullptr;
-  int* pf = nullptr;
-  double* pp = nullptr;
-  rc |= dalloc(x, &off, n_groups + 1);
-  rc |= dalloc(x, &dobs, (size_t)n_obs * n_fields + 4);   // (+32 B: staged-row DMA slack)
-  rc |= dalloc(x, &pf, n_params);
-  rc |= dalloc(x, &pp, (size_t)8 * n_params);
-  // (+72 C + 128 slack: the Gibbs wave reads 72 groups' values unconditionally, and the
-  // payload copies read whole 64-chain rows of the last group)
-  rc |= dalloc(x, &d.vb0, PGC + (size_t)72 * n_chains + 128);
-  rc |= dalloc(x, &d.vb1, PGC + (size_t)72 * n_chains + 128);
-  rc |= dalloc(x, &d.lp, PGC);
-  rc |= dalloc(x, &d.ll, GC);
-  rc |= dalloc(x, &d.scale, PGC);
-  rc |= dalloc(x, &d.nacc, PGC);
-  rc |= dalloc(x, &d.nrej, PGC);
-  rc |= dalloc(x, &d.tacc, PGC);
-  // hyper-parameters after iteration t live in slot t & 1 ([2][P][C]), like the values
-  rc |= dalloc(x, &d.mu, 2 * PC);
-  rc |= dalloc(x, &d.s2, 2 * PC);
-  rc |= dalloc(x, &d.hsd, 2 * PC);
-  rc |= dalloc(x, &d.hlsd, 2 * PC);
-  if (rc) { nmc_destroy(x); return rc; }
-  d.off = off; d.obs = dobs; d.pfam = pf; d.ppar = pp;
-  d.C = n_chains; d.G = n_groups; d.P = n_params; d.pooling = pooling; d.nf = n_fields;
-  d.chain_base = chain_base; d.rng_mode = rng_mode; d.seed = seed;
-  d.CB = (n_chains + 63) / 64;
-  d.ha = (n_groups - 1) / 2.0;
-  d.hlga = lgamma(d.ha > 0 ? d.ha : 1.0);
-  {
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0)
-      x->ncu = prop.multiProcessorCount;
-  }
-  x->nacc = ll_family == NMC_LL_GAUSS_MEAN ? n_fields : 1;
-  if (ll_family >= NMC_LL_USER_BASE) {   // runtime-compiled family: module + constants
-    if (int rc0 = nmc_user_attach(x, ll_family)) { nmc_destroy(x); return rc0; }
-    if (n_ll_consts > 0) {
-      if (int rc0 = dalloc(x, &x->user_k, (size_t)n_ll_consts)) { nmc_destroy(x); return rc0; }
-      HIPCHK(hipMemcpy(x->user_k, ll_consts, (size_t)n_ll_consts * 8, hipMemcpyHostToDevice));
-    }
-  }
-  // numpy pairwise-sum plan of the hyper update (partial pooling)
-  std::vector<int> starts, merges;
-  pairwise_plan(0, n_groups, starts, merges);
-  int ntail = 0;
-  for (size_t k = 0; k < starts.size(); ++k) {
-    const int m = (k + 1 < starts.size() ? starts[k + 1] : n_groups) - starts[k];
-    const int m8 = m >= 8 ? m - m % 8 : 0;
-    ntail = std::max(ntail, m - m8);
-  }
-  starts.push_back(n_groups);
-  d.nleaf = (int)starts.size() - 1;
-  d.nmerge = (int)merges.size() / 2;
-  d.ntail = ntail;
-  int* dleaf = nullptr;
-  int* dmerge = nullptr;
-  rc |= dalloc(x, &dleaf, starts.size());
-  rc |= dalloc(x, &dmerge, merges.size());
-  // [RB][P][8 shards][32], RB <= ceil(C / 32)
-  rc |= dalloc(x, &d.cnt, cnt_bytes(x) / sizeof(unsigned));
-  rc |= dalloc(x, &d.hrd, hrd_words(x));
-  // Dev.gsep role words [RB <= ceil(C / 32)][16] and the fallback count
-  rc |= dalloc(x, &d.grole, grole_words(x));
-  rc |= dalloc(x, &d.gfb, 32);
-  if (rc) { nmc_destroy(x); return rc; }
-  {
-    void* h = nullptr;
-    void* dp = nullptr;
-    e = hipHostMalloc(&h, 64, hipHostMallocCoherent | hipHostMallocMapped);
-    if (e == hipSuccess) x->tmo_host = (volatile unsigned*)h;
-    if (e == hipSuccess) e = hipHostGetDevicePointer(&dp, h, 0);
-    if (e != hipSuccess) {
-      nmc_destroy(x);
-      return fail(-2, std::string("timeout word (pinned host memory): ") + hipGetErrorString(e));
-    }
-    memset(h, 0, 64);
-    d.tmo = (unsigned*)dp;
-  }
-  HIPCHK(hipMemset(d.cnt, 0, cnt_bytes(x)));
-  HIPCHK(hipMemset(d.hrd, 0, hrd_words(x) * sizeof(unsigned)));
-  HIPCHK(hipMemset(d.grole, 0, grole_words(x) * sizeof(unsigned long long)));
-  HIPCHK(hipMemset(d.gfb, 0, 32 * sizeof(unsigned)));
-  d.pbase = d.xbase = 0;
-  // Dev.gsep: how long the two kernels may take to meet before the likelihood workgroups take
-  // a launch's Gibbs tasks over (NMC_GSEP_PATIENCE_US, default 20 ms: 2 ms was sometimes too
-  // short for the Gibbs kernel to be dispatched beside a running step kernel and the variate
-  // fill, and a launch fell back while both kernels ran -- the same results, slower);
-  // NMC_GSEP_SERIAL (tests) serializes them on one stream
-  d.gep = 0;
-  d.gpat = 2000000u;
-  if (const char* e = getenv("NMC_GSEP_PATIENCE_US")) d.gpat = (unsigned)(atol(e) * 100);
-  x->gserial = nmc_env_int("NMC_GSEP_SERIAL", 0);
-  // nmc_k_fill's grid: 3 blocks of 256 per CU (its Philox instance's 140 VGPRs: three waves
-  // per SIMD); NMC_FILL_BPC overrides (A/B)
-  x->fill_bpc = std::max(1, nmc_env_int("NMC_FILL_BPC", 3));
-  // the pipelined fill beside a step kernel: one block per CU (one wave per SIMD next to the
-  // step kernel's), NMC_PREFILL_BPC overrides; NMC_PREFILL=0 turns the pipelining off (A/B)
-  x->prefill_bpc = std::max(1, nmc_env_int("NMC_PREFILL_BPC", 1));
-  x->prefill_on = nmc_env_flag("NMC_PREFILL", true);
-  d.leaf = dleaf;
-  d.merge = dmerge;
-  HIPCHK(hipMemcpy(dleaf, starts.data(), starts.size() * sizeof(int), hipMemcpyHostToDevice));
-  if (!merges.empty())
-    HIPCHK(hipMemcpy(dmerge, merges.data(), merges.size() * sizeof(int), hipMemcpyHostToDevice));
-  int64_t nmax = 0;
-  for (int g = 0; g < n_groups; ++g)
-    nmax = std::max<int64_t>(nmax, group_offsets[g + 1] - group_offsets[g]);
-  x->nmax_group = nmax;
-  // Row split: groups far larger than one workgroup's 64 KiB LDS row area are shared by S
-  // workgroups, at most 64 and at most one per CU of a full MI355X (256 CUs) per group.
-  // S depends on (rows, fields, groups) only -- never on the chain count or on the
-  // device's CU count -- so the partial-sum order, and every result, is the same whatever
-  // the sharding, the launch batching or the GPU partition (a partition too small to
-  // hold the S members of one group at once refuses the run: nmc_create below).
-  d.S = 1;
-  d.cb0 = 0;
-  {
-    const int64_t target = std::max<int64_t>(256, (64 * 1024) / (n_fields * 8));
-    if (nmax > 2 * target)
-      d.S = (int)std::min<int64_t>({64, (nmax + target - 1) / target,
-                                    std::max<int64_t>(1, NMC_SPLIT_CU_BASIS / n_groups)});
-#ifdef NMC_DEBUG_KNOBS   // (diagnostic builds only: changes the summation order)
-    if (const int v = nmc_env_int("NMC_SPLIT", 0); v >= 1 && v <= 256) d.S = v;
-#endif
-  }
-  d.nmax = (int)((nmax + d.S - 1) / d.S);   // rows of the largest member
-  choose_geometry(x);
-  if (run_lds_bytes(x) > (size_t)160 * 1024) {
+  // (every failure from here on leaves through the one nmc_destroy)
+  if (int rc = create_on_device(x, group_offsets, obs, prior_family, prior_params)) {
     nmc_destroy(x);
-    return fail(-1, "workgroup state exceeds the 160 KiB LDS of a CU (too many parameters, "
-                    "groups or rows per group)");
+    return rc;
   }
-  if (pooling == NMC_POOL_PARTIAL) {
-    NmcCall c;
-    c.op = NMC_OP_CAN_PERSIST;
-    if (int rc2 = nmc_call_family(x, c)) { nmc_destroy(x); return rc2; }
-    if (x->sweep && c.result != 1 && run_mode(x) == NMC_MODE_SYNC_OWN && !d.gsep &&
-        x->family < NMC_LL_USER_BASE && !getenv("NMC_GSEP")) {
-      // the likelihood and Gibbs workgroups in one grid do not fit: two kernels, one per
-      // stream (nmc_k_sweep + nmc_k_sweep_gibbs), each workgroup with its own LDS size
-      d.gsep = 1;
-      if (int rc2 = nmc_call_family(x, c)) { nmc_destroy(x); return rc2; }
-    }
-    if (x->sweep && c.result != 1) {   // the sweep grid cannot be resident: nmc_k_run
-      x->no_sweep = true;
-      choose_geometry(x);
-      if (int rc2 = nmc_call_family(x, c)) { nmc_destroy(x); return rc2; }
-    }
-    // row split: always persistent (the members exchange every step), in resident batches
-    // of chain blocks when the whole grid is not (chain blocks are independent)
-    x->persistent = c.result == 1 || d.S > 1;
-  }
-  // XCD-aware placement of nmc_k_run's persistent partial-pooling grid (Dev.xpc, NMC_XMAP=1):
-  // the RB chain blocks on 8 / RB XCDs each, when RB divides 8 and the groups split evenly.
-  // Measured 1.5-2.5 % slower at cfg 3 than chain-block-major (profiles/r06/r06n_*): off
-  d.xpc = 0;
-  if (pooling == NMC_POOL_PARTIAL && x->persistent && !x->sweep && d.S == 1 && d.RB <= 8 &&
-      8 % d.RB == 0 && n_groups % (8 / d.RB) == 0 && nmc_env_int("NMC_XMAP", 0) == 1)
-    d.xpc = 8 / d.RB;
-  if (d.S > 1) {   // row split: resident batches of chain blocks, exchange buffers
-    NmcCall c;
-    c.op = NMC_OP_CAPACITY;
-    if (int rc2 = nmc_call_family(x, c)) { nmc_destroy(x); return rc2; }
-    const int64_t per_cb = (int64_t)d.G * d.S;
-    if (c.result < per_cb) {
-      nmc_destroy(x);
-      return fail(-1, "row split: the S workgroups of one group are not co-resident");
-    }
-    x->split_batch = (int)std::min<int64_t>(d.RB, c.result / per_cb);
-    if (const int v = nmc_env_int("NMC_SPLIT_BATCH", 0); v >= 1 && v < x->split_batch)
-      x->split_batch = v;
-    rc |= dalloc(x, &d.xbuf, (size_t)2 * d.RB * d.G * d.S * x->nacc * 64);
-    rc |= dalloc(x, &d.xcnt, (size_t)d.RB * d.G * 32);
-    if (rc) { nmc_destroy(x); return rc; }
-    HIPCHK(hipMemset(d.xcnt, 0, (size_t)d.RB * d.G * 32 * sizeof(unsigned)));
-  }
-  // build option NMC_ZIN_BUILD=1: the step kernel draws its {z, log u} itself (a job in
-  // each step's tile queue) unless the opt-in one-barrier kernel runs (it DMAs them from
-  // the fill's ring); NMC_ZIN=0 keeps the fill (bit-identical; tests compare them)
-  d.zin = NMC_ZIN_BUILD && nmc_env_flag("NMC_ZIN", true);
-  // nmc_k_sweep: every variate drawn in the kernel (NMC_ZIN=1) or from the fill's ring
-  if (x->sweep) d.zin = nmc_env_flag("NMC_ZIN", false);
-  d.thin = 1; d.tune_interval = 100;
-  HIPCHK(hipMemcpy(off, group_offsets, (n_groups + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
-  if (n_obs > 0)
-    HIPCHK(hipMemcpy(dobs, obs, (size_t)n_obs * n_fields * sizeof(double), hipMemcpyHostToDevice));
-  if (prior_family) HIPCHK(hipMemcpy(pf, prior_family, n_params * sizeof(int), hipMemcpyHostToDevice));
-  if (prior_params) HIPCHK(hipMemcpy(pp, prior_params, 8 * n_params * sizeof(double), hipMemcpyHostToDevice));
-  HIPCHK(hipMemset(d.nacc, 0, PGC * sizeof(int)));
-  HIPCHK(hipMemset(d.nrej, 0, PGC * sizeof(int)));
-  HIPCHK(hipMemset(d.tacc, 0, PGC * sizeof(long long)));
-  std::vector<double> ones(PGC, 1.0);
-  HIPCHK(hipMemcpy(d.scale, ones.data(), PGC * sizeof(double), hipMemcpyHostToDevice));
   *out = x;
   return 0;
 }

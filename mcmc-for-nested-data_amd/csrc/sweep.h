@@ -1,5 +1,7 @@
-// sweep.h -- nmc_k_sweep<Fam, MODE>: the step kernel for groups whose rows fit LDS and need
-// no row split, in three waves per SIMD.
+// sweep.h -- nmc_k_sweep<Fam>: the step kernel of partial pooling over G > 128 groups (up to
+// four numpy leaves; cfg 4) whose rows fit LDS and need no row split, in three waves per
+// SIMD.  The host reports its mode as NMC_MODE_SYNC_OWN (step.h); its Gibbs side is
+// sweep_gibbs.h.
 //
 // Same work, tile partition, summation orders, variates and outputs as nmc_k_run
 // (step.h) -- the two are bit-identical and the tests compare them -- built around what
@@ -9,38 +11,34 @@
 // waves leave the SIMDs of its control and Gibbs waves with one likelihood wave for most
 // of a step; here 12 waves (768 threads, <= 168 VGPRs) keep two or three likelihood waves
 // on every SIMD while the roles run.  The kernel holds few values across its persistent
-// loop: Dev is read through a pointer laundered at the top of every step (nmc_kdev), and
-// each role's values live in its own branch (the Gibbs wave's 64-value payload never shares
-// registers with the row loop).  The variates come from nmc_k_fill's ring (the control wave
-// LDS-DMAs each next step's {z, log u}; the Gibbs wave reads its task's pair), or, with
-// Dev.zin, are drawn inside the kernel (the fill's own functions, so the same bits):
+// loop: Dev is read through a pointer laundered at the top of every step
+// (nmc_sweep_args_at), and each role's values live in its own branch.  The variates come
+// from nmc_k_fill's ring (the control wave LDS-DMAs each next step's {z, log u}; a Gibbs
+// task's pair is read by whoever updates it), or, with Dev.zin, are drawn inside the kernel
+// (the fill's own functions, so the same bits):
 //   * {z, log u} of step (t, p) (Parameter.propose :304-306, the accept uniform :362):
 //     entries 0-2 of the previous step's tile queue (radius, cosine, log u);
-//   * {hyper z, Gamma((G-1)/2)} of a Gibbs task (HyperParameter.update :481-498): drawn by
-//     the Gibbs wave for its own task.
+//   * {hyper z, Gamma((G-1)/2)} of a Gibbs task (HyperParameter.update :481-498): drawn
+//     where the task is updated.
 //
-// MODE (step.h NMC_MODE_*):
-//   NOPOOL    none / complete pooling, 64 chains per workgroup
-//   HALF      none / complete pooling, 32 chains per workgroup (lanes l, l + 32: one chain)
-//   SYNC_REG  partial pooling, G <= 64: the Gibbs wave fetches a task's G published values
-//             into registers (one sc1 round trip) -- nmc_k_run's register hand-off
-//   SYNC_LDS  partial pooling, 64 < G <= 128 (one numpy leaf): the same hand-off with the
-//             payload moved to LDS by LDS-DMA, updated from there (nmc_hyper_compute)
-//   SYNC_OWN  partial pooling, G > 128 (up to four numpy leaves): RB * P extra workgroups in
-//             the grid, one per (chain block, parameter), compute each Gibbs task ONCE for the
-//             chain block (every wave streaming its numpy streams' values with sc1 loads, all
-//             in flight; nmc_hyper) and publish the four hyper values write-through with a
-//             ready count; each likelihood workgroup's Gibbs wave only polls that count and
-//             reads the four values (nmc_hyper_read) -- instead of every one of the G
-//             workgroups streaming the chain block's G values itself
+// The Gibbs update: RB * P Gibbs workgroups, one per (chain block, parameter), compute each
+// Gibbs task ONCE for the chain block (every wave streaming its numpy streams' values with
+// sc1 loads, all in flight) and publish the four hyper values write-through with a ready
+// count; each likelihood workgroup's Gibbs wave only polls that count and reads the four
+// values (nmc_hyper_read) -- instead of every one of the G workgroups streaming the chain
+// block's G values itself.  The Gibbs workgroups are the blocks after the RB * G likelihood
+// workgroups of this kernel's grid, or, with Dev.gsep, the kernel nmc_k_sweep_gibbs on a
+// second stream (then a likelihood workgroup's Gibbs wave can take the updates over:
+// sweep_gibbs.h, nmc_grole_*).
 // Wave roles per step k = (t, p):
 //   wave 0   control: the deferred state update of step k-1, the decision's operands (both
 //            counter outcomes, tuned scales, priors), the count of the last published value;
 //            then likelihood tiles; after barrier A the slot sum, finish and the Metropolis
-//            decision (:334-383), published write-through (partial pooling)
-//   wave 1   (partial) Gibbs: task k - lag (poll, fetch, pairwise update, this step's priors
-//            when they need it), then barrier A / B with the others
-//   others   likelihood tiles from the step's LDS queue (entry 0: the next step's variates)
+//            decision (:334-383), published write-through
+//   wave 1   Gibbs: task k - lag (poll its ready count, read the hyper values, this step's
+//            priors when they need it), then barrier A / B with the others
+//   others   the W - 2 queue waves: likelihood tiles from the step's LDS queue (its first
+//            entries, with Dev.zin: the next step's variates)
 #pragma once
 #include "kernels.h"
 
@@ -54,9 +52,8 @@ struct nmc_sweep_layout {
   int th;     // [P]            current values
   int part;   // [NACC][NSLOT]  tile partial sums (unused slots: -0.0)
   int st;     // [5][P]         scale, log prior, n acc, n rej, total acc (NMC_ST_*)
-  int hyp;    // [6][P]         hyper state (NMC_HY_*), partial pooling
-  int hval;   // [G + 1]        SYNC_LDS: the Gibbs payload (+1: the DMA moves group pairs)
-  int zl;     // [2][2]         {z, log u} of this and the next step (step parity)
+  int hyp;    // [6][P]         hyper state (NMC_HY_*)
+  int zl;     // [2][2]        {z, log u} of this and the next step (step parity)
   int zm;     // [2]            the proposal normal's second factor by step parity: z is
               //                zl's z times zm (1.0 with the fill's ring; with Dev.zin the
               //                Box-Muller radius and cosine are two queue jobs)
@@ -67,16 +64,14 @@ struct nmc_sweep_layout {
   int rows;   // [nrows][NF]    the group's rows, staged once per launch
   int total;  // columns
 };
-__host__ __device__ inline nmc_sweep_layout nmc_sweep_lds(int nacc, int P, int partial,
-                                                          int hlds, int G, int row_doubles) {
+__host__ __device__ inline nmc_sweep_layout nmc_sweep_lds(int nacc, int P, int row_doubles) {
   nmc_sweep_layout L;
   L.flag = 0;   // (first: its step constants, NMC_SWK_*, sit at a fixed address)
   L.th = 1;
   L.part = L.th + P;
   L.st = L.part + nacc * NMC_NSLOT;
   L.hyp = L.st + 5 * P;
-  L.hval = L.hyp + (partial ? 6 * P : 0);
-  L.zl = L.hval + (partial && hlds ? G + 1 : 0);
+  L.zl = L.hyp + 6 * P;
   L.zm = L.zl + 4;
   L.cw = L.zm + 2;
   L.rows = L.cw + 8;
@@ -85,19 +80,21 @@ __host__ __device__ inline nmc_sweep_layout nmc_sweep_lds(int nacc, int P, int p
   return L;
 }
 
-// Out-of-line helpers: the variate draws and the none/complete-pooling priors run once per
-// step on one wave; kept out of the step loop's body so their many polynomial constants are
-// materialized where they are used rather than hoisted into registers for the whole launch.
 // The step constants: ints at word NMC_SWK_AT of LDS column 0 (the flag column), written
 // once by the prologue (after the column is zeroed) -- the problem
 // sizes, the group's row count and tiling and the carve's offsets -- so a step derives its
 // view with a few broadcast LDS reads at a fixed address (no kernel-argument or global load
 // on the step's critical path)
+// (NMC_SWK_RSV: the slot of a removed carve offset, still written (L.zl) and read so that the
+//  machine code stays what was measured; drop it with the next change of this kernel's code)
 enum { NMC_SWK_P = 0, NMC_SWK_G, NMC_SWK_C, NMC_SWK_NGRP, NMC_SWK_N, NMC_SWK_NT, NMC_SWK_H,
-       NMC_SWK_A, NMC_SWK_B, NMC_SWK_TH, NMC_SWK_PART, NMC_SWK_ST, NMC_SWK_HYP, NMC_SWK_HVAL,
+       NMC_SWK_A, NMC_SWK_B, NMC_SWK_TH, NMC_SWK_PART, NMC_SWK_ST, NMC_SWK_HYP, NMC_SWK_RSV,
        NMC_SWK_ZL, NMC_SWK_ZM, NMC_SWK_CW, NMC_SWK_FLAG, NMC_SWK_ROWS, NMC_SWK_TOTAL,
        NMC_SWK_COUNT = 20, NMC_SWK_AT = 32 };
 
+// Out-of-line helpers: the variate draws run once per step on one wave; kept out of the step
+// loop's body so their many polynomial constants are materialized where they are used rather
+// than hoisted into registers for the whole launch.
 // Part j of the variates of step (it, p) of group g, chain c, nmc_step_variate's values
 // split three ways so three waves draw them side by side (each ~1/3 of the ~460 VALU
 // instructions): j = 0 the Box-Muller radius sqrt(-2 log(1 - ua)), j = 1 its cosine
@@ -137,9 +134,6 @@ __device__ __noinline__ nmc_d2 nmc_sweep_hyper_variate(const double* rhz, const 
   }
   return r;
 }
-__device__ __noinline__ double nmc_sweep_prior(int fam, const double* prm, double x) {
-  return nmc_prior_logpdf(fam, prm, x);
-}
 
 // The kernel's only argument (one struct, so the kernarg segment holds it at offset 0 and
 // every field is read through the laundered pointer of nmc_sweep_args_at).
@@ -157,419 +151,14 @@ __device__ __forceinline__ const nmc_sweep_args<Fam>* nmc_sweep_args_at() {
   return (const nmc_sweep_args<Fam>*)q;
 }
 
-// HyperParameter.update (:463-498) of parameter q for one chain block, as nmc_hyper<SC1, NS,
-// true> (the same streams, sums and order, so the same bits) but loading the G values once:
-// each wave keeps its NS streams' values in registers for the second pass (sum of squares
-// about the new mean) instead of fetching them again -- one device-scope round trip per
-// task instead of two.  The tail stream's raw values wait in LDS (pass 1 writes them).
-template <int NS>
-__device__ __forceinline__ void nmc_hyper_once(const Dev& d, const double* src, int cb, int t,
-                                               double* lds, const nmc_lds_layout& L, int q) {
-  const int lane = threadIdx.x & 63;
-  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int W = blockDim.x >> 6;
-  const int P = d.P, G = d.G, C = d.C, nl = d.nleaf, ncol = 8 + d.ntail;
-  const int per = 8 + (d.ntail ? 1 : 0);
-  const int c = nmc_lane_chain(d, cb, lane);
-  const int cc = c < C ? c : C - 1;
-  const int sbeg = q * nl * per, nst = (q + 1) * nl * per;
-  struct Strm {
-    int j, pl, m, m8;
-    const double* xp;
-  };
-  auto strm = [&](int s) {
-    Strm r;
-    r.j = s % per;
-    r.pl = s / per;
-    const int lf = r.pl % nl;
-    const int a = nl == 1 ? 0 : d.leaf[lf];
-    r.m = nl == 1 ? G : d.leaf[lf + 1] - a;
-    r.m8 = r.m >= 8 ? r.m - r.m % 8 : 0;
-    r.xp = src + ((size_t)q * G + a) * C + cc;
-    return r;
-  };
-  // one round: this wave's streams w, w + W, ..., w + (NS-1) W of [sbeg, nst)
-  static_assert(NS >= 1, "streams per wave");
-  double v[NS][16];
-#pragma unroll
-  for (int k = 0; k < NS; ++k) {
-    const int s = sbeg + w + k * W;
-    const Strm r = strm(s < nst ? s : sbeg);
-    const int cnt = s < nst && r.j < 8 ? r.m8 >> 3 : 0;
-#pragma unroll
-    for (int u = 0; u < 16; ++u)
-      v[k][u] = u < cnt ? nmc_ldv<NMC_SRC_SC1>(r.xp + (size_t)(r.j + 8 * u) * C) : 0.0;
-  }
-  auto pass = [&](bool sq) {
-    const double mu = sq ? lds[(L.hyp + NMC_HY_MU * P + q) * 64 + lane] : 0.0;
-#pragma unroll
-    for (int k = 0; k < NS; ++k) {
-      const int s = sbeg + w + k * W;
-      if (s >= nst) continue;
-      const Strm r = strm(s);
-      double* out = lds + (size_t)(L.hst + r.pl * ncol) * 64 + lane;
-      if (r.j < 8) {
-        const int cnt = r.m8 >> 3;
-        double acc = 0.0;
-#pragma unroll
-        for (int u = 0; u < 16; ++u) {
-          if (u < cnt) {
-            double x = v[k][u];
-            if (sq) {
-              x = x - mu;
-              x = x * x;
-            }
-            acc = u == 0 ? x : acc + x;
-          }
-        }
-        out[r.j * 64] = acc;
-      } else {   // the tail: raw values in pass 1, their squares about mu in pass 2
-        for (int u = r.m8; u < r.m; ++u) {
-          double x = sq ? out[(8 + u - r.m8) * 64] : nmc_ldv<NMC_SRC_SC1>(r.xp + (size_t)u * C);
-          if (sq) {
-            x = x - mu;
-            x = x * x;
-          }
-          out[(8 + u - r.m8) * 64] = x;
-        }
-      }
-    }
-  };
-  // (a wave holds NS streams: the whole parameter's streams in one round)
-  pass(false);
-  __syncthreads();
-  if (w == 0) {
-    const double tot = nmc_hyper_combine(d, lds, L, q, lane);
-    const double sdm = lds[(L.hyp + NMC_HY_SDM * P + q) * 64 + lane];
-    const double hz = lds[L.hv * 64 + (q * 64 + lane) * 2];
-    lds[(L.hyp + NMC_HY_MU * P + q) * 64 + lane] = tot / G + sdm * hz;   // mu ~ N(mean, s2/G)
-  }
-  __syncthreads();
-  pass(true);
-  __syncthreads();
-  if (w == 0) {
-    const bool own = nmc_lane_owns(d, c, lane);
-    const int row = nmc_record_row(d, t);
-    const double ss = nmc_hyper_combine(d, lds, L, q, lane);
-    const double hat = ss / (double)(G - 1);
-    const double scale = d.ha * hat;
-    const double hx = lds[L.hv * 64 + (q * 64 + lane) * 2 + 1];
-    // scipy invgamma.rvs: (1/gammainccinv(a, U)) * scale + loc; loc when scale == 0
-    const double s2n = scale == 0.0 ? 0.0 : (1.0 / hx) * scale;
-    const double sdn = sqrt(s2n);
-    const double lsd = log(sdn);
-    const double m = lds[(L.hyp + NMC_HY_MU * P + q) * 64 + lane];
-    lds[(L.hyp + NMC_HY_SD * P + q) * 64 + lane] = sdn;
-    lds[(L.hyp + NMC_HY_LSD * P + q) * 64 + lane] = lsd;
-    lds[(L.hyp + NMC_HY_S2 * P + q) * 64 + lane] = s2n;
-    lds[(L.hyp + NMC_HY_ISD * P + q) * 64 + lane] = 1.0 / sdn;
-    if (own) {
-      const size_t ho = nmc_hslot(d, t) + (size_t)q * C + c;
-      __hip_atomic_store(d.mu + ho, m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(d.s2 + ho, s2n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(d.hsd + ho, sdn, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(d.hlsd + ho, lsd, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (row >= 0) {
-        double* out = d.samples + ((size_t)row * d.cols + (size_t)q * (G + 2)) * C + c;
-        out[0] = m;
-        out[C] = s2n;
-      }
-    }
-  }
-}
+#include "sweep_gibbs.h"
 
-// ---- Dev.gsep without co-scheduling ----
-// The two kernels of the gsep path each wait on counters only the other advances, and HIP
-// does not promise that kernels on two streams run at the same time (a profiler's PMC pass,
-// AMD_SERIALIZE_KERNEL or a shared hardware queue serialize them).  So each chain block of a
-// launch has a role word (Dev.grole, epoch = Dev.gep): a Gibbs workgroup marks itself
-// started once its first task's values are published; if no Gibbs workgroup of the chain
-// block has started within Dev.gpat ticks, whichever side notices first sets the fallback
-// bit.  Then the Gibbs workgroups leave, and the likelihood workgroups' Gibbs waves update
-// every task of the launch themselves (nmc_hyper_update_stream: the same sums, draws and
-// outputs, so the same bits), group 0's writing and counting them as the Gibbs workgroup
-// would.  Either every task of a (launch, chain block) comes from the Gibbs kernel or every
-// one from the fallback: the bit is only set while no Gibbs workgroup has started.
-__device__ __forceinline__ unsigned long long* nmc_grole(const Dev& d, int cb) {
-  return d.grole + (size_t)cb * 16;
-}
-__device__ __forceinline__ bool nmc_grole_is_fallback(const Dev& d, unsigned long long v) {
-  return (unsigned)(v >> 32) == d.gep && (v & 1ull);
-}
-// (one lane) set the fallback bit of this launch; false: a Gibbs workgroup has started
-__device__ __forceinline__ bool nmc_grole_fallback(const Dev& d, int cb) {
-  unsigned long long* r = nmc_grole(d, cb);
-  const unsigned long long ep = (unsigned long long)d.gep << 32;
-  unsigned long long v = __hip_atomic_load(r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  for (;;) {
-    if ((unsigned)(v >> 32) == d.gep) {
-      if (v & 1ull) return true;
-      if (v != ep) return false;   // started
-    }
-    if (__hip_atomic_compare_exchange_strong(r, &v, ep | 1ull, __ATOMIC_RELAXED,
-                                             __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
-      __hip_atomic_fetch_add(d.gfb, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      return true;
-    }
-  }
-}
-// (one lane) a Gibbs workgroup starts its first task; false: the fallback is set, leave
-__device__ __forceinline__ bool nmc_grole_start(const Dev& d, int cb) {
-  unsigned long long* r = nmc_grole(d, cb);
-  const unsigned long long ep = (unsigned long long)d.gep << 32;
-  unsigned long long v = __hip_atomic_load(r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  for (;;) {
-    unsigned long long nv = ep + 2ull;
-    if ((unsigned)(v >> 32) == d.gep) {
-      if (v & 1ull) return false;
-      nv = v + 2ull;
-    }
-    if (__hip_atomic_compare_exchange_strong(r, &v, nv, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
-                                             __HIP_MEMORY_SCOPE_AGENT))
-      return true;
-  }
-}
-// The calling wave's patience clock (s_memrealtime: 100 MHz, one clock for the chip).
-__device__ __forceinline__ bool nmc_grole_patience_over(const Dev& d, unsigned long long t0) {
-  return __builtin_amdgcn_s_memrealtime() - t0 > (unsigned long long)d.gpat;
-}
-// A Gibbs workgroup's wait for its FIRST task's publications (wave 0; wave-uniform result):
-// 1 go on (started), 0 leave (the fallback is set, or a timeout recorded in d.tmo).
-__device__ __forceinline__ int nmc_grole_first_wait(const Dev& d, int cb, int q, unsigned target) {
-  const int lane = threadIdx.x & 63;
-  target += (unsigned)d.G * d.pbase;
-  unsigned* ctr = nmc_counter(d, cb, q, lane & 7);
-  const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-  bool patient = true;
-  for (unsigned spins = 0;; ++spins) {
-    const unsigned v =
-        lane < 8 ? __hip_atomic_load(ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
-    unsigned tot = 0;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) tot += __builtin_amdgcn_readlane(v, k);
-    if (tot >= target) {
-      const bool go = lane == 0 ? nmc_grole_start(d, cb) : false;
-      return __builtin_amdgcn_readlane((int)go, 0);
-    }
-    if ((spins & 63) == 63) {
-      const unsigned long long rv =
-          __hip_atomic_load(nmc_grole(d, cb), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (nmc_grole_is_fallback(d, rv)) return 0;
-      if (patient && nmc_grole_patience_over(d, t0)) {
-        const bool fb = lane == 0 ? nmc_grole_fallback(d, cb) : false;
-        if (__builtin_amdgcn_readlane((int)fb, 0)) return 0;
-        patient = false;   // a sibling has started: the likelihood kernel runs, wait for it
-      }
-    }
-    if ((spins & 255) == 255 &&
-        __hip_atomic_load(d.tmo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0)
-      return 0;
-    if (spins >= NMC_SPIN_LIMIT) {
-      __hip_atomic_store(d.tmo, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      return 0;
-    }
-    __builtin_amdgcn_s_sleep(2);
-  }
-}
-// A likelihood workgroup's Gibbs wave waiting for task (cb, q)'s ready count (wave-uniform):
-// 1 ready, -1 fallback (update it here), 0 timeout (d.tmo).
-__device__ __forceinline__ int nmc_grole_own_wait(const Dev& d, int cb, int q, unsigned target) {
-  const int lane = threadIdx.x & 63;
-  const unsigned* ctr = nmc_hrd(d, cb, q);
-  const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-  bool patient = true;
-  for (unsigned spins = 0;; ++spins) {
-    if (__hip_atomic_load(ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= target) return 1;
-    if ((spins & 63) == 63) {
-      const unsigned long long rv =
-          __hip_atomic_load(nmc_grole(d, cb), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (nmc_grole_is_fallback(d, rv)) return -1;
-      if (patient && nmc_grole_patience_over(d, t0)) {
-        const bool fb = lane == 0 ? nmc_grole_fallback(d, cb) : false;
-        if (__builtin_amdgcn_readlane((int)fb, 0)) return -1;
-        patient = false;   // a Gibbs workgroup has started: wait as long as it takes
-      }
-    }
-    if ((spins & 255) == 255 &&
-        __hip_atomic_load(d.tmo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0)
-      return 0;
-    if (spins >= NMC_SPIN_LIMIT) {
-      __hip_atomic_store(d.tmo, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      return 0;
-    }
-    __builtin_amdgcn_s_sleep(2);
-  }
-}
-// The fallback's update of task (tq, q) by one wave: HyperParameter.update (:463-498) with
-// the values streamed from global memory (sc1) in 8-value chunks -- nmc_pairwise_stream,
-// the order of nmc_hyper / nmc_hyper_once -- and the task's variates from the fill's ring or
-// drawn here (Dev.zin).  write: the global slot of tq and the sample row (group 0's wave).
-// Inlined, with short chunks: a rare path (the Gibbs kernel did not run beside the sweep)
-// whose registers must not cost the likelihood loop -- as a call it added 58 SGPR spills and
-// 128 B of scratch to the cfg-4 instance; inlined with 32-value chunks, one VGPR spill.
-__device__ __forceinline__ void nmc_hyper_update_stream(const Dev& d, int cb, int tq, int q,
-                                                     int cc, double* lds, int hyp, bool write) {
-  const int lane = threadIdx.x & 63;
-  const int P = d.P, G = d.G, C = d.C;
-  const double* src = ((tq & 1) ? d.vb1 : d.vb0) + (size_t)q * G * C + cc;
-  nmc_d2 hv;
-  if (d.zin) {
-    hv = nmc_sweep_hyper_variate(d.rhz, d.rhu, d.replay_n, d.rng_mode, P, C,
-                                 (uint32_t)(d.chain_base + cc), d.seed, d.ha, d.hlga, tq, q, cc);
-  } else {
-    const size_t hvi = (((size_t)(tq - d.vbase) * P + q) * C + cc) * 2;
-    hv.a = d.vh[hvi];
-    hv.b = d.vh[hvi + 1];
-  }
-  const double sdm = sqrt(lds[(hyp + NMC_HY_S2 * P + q) * 64 + lane] / G);
-  const double tot = nmc_pairwise_stream<8>(d, src, false, 0.0);
-  const double mu = tot / G + sdm * hv.a;                        // mu ~ N(mean(x), sqrt(s2/G))
-  const double ss = nmc_pairwise_stream<8>(d, src, true, mu);
-  nmc_hyper_finish(d, cb, tq, q, lds, hyp, write, mu, ss, hv.b);
-}
-
-// SYNC_OWN's Gibbs workgroup kb = (chain block, parameter q), four waves: every task (t, q)
-// of the launch in order, once its publication is complete -- HyperParameter.update
-// (:463-498) computed once per chain block, written through and counted ready (nmc_hrd)
-// for the likelihood workgroups' Gibbs waves.
-// GW: the waves of the Gibbs kernel of its own (nmc_k_sweep_gibbs: the one-load update, four
-// streams per wave on 4 waves, two on 8); 0: inside nmc_k_sweep, where the update streams its
-// values twice (168-VGPR budget shared with the likelihood code).
-template <class Fam, int GW>
-__device__ __forceinline__ void nmc_sweep_gibbs_wg(int kb, double* lds) {
-  const nmc_sweep_args<Fam>* A = nmc_sweep_args_at<Fam>();
-  const int lane = threadIdx.x & 63;
-  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int W = blockDim.x >> 6;
-  const int i0 = A->i0, i1 = A->i1;
-#define d (A->d)
-  const int P = d.P, G = d.G, C = d.C;
-  const int hcb = d.cb0 + kb / P, q = kb % P;
-  const int c = hcb * 64 + lane;
-  const int cc = c < C ? c : C - 1;
-  const nmc_lds_layout H = nmc_lds(0, P, 1, d.nleaf, d.ntail, W, G, 0, 0);
-  double* hy = lds + H.hyp * 64 + lane;
-  if (w == 0) {   // the state of q after iteration i0-1 (slot (i0-1) & 1)
-    const size_t ho = nmc_hslot(d, i0 - 1) + (size_t)q * C + cc;
-    hy[(NMC_HY_MU * P + q) * 64] = d.mu[ho];
-    hy[(NMC_HY_SD * P + q) * 64] = d.hsd[ho];
-    hy[(NMC_HY_LSD * P + q) * 64] = d.hlsd[ho];
-    hy[(NMC_HY_S2 * P + q) * 64] = d.s2[ho];
-  }
-#ifdef NMC_STAMPS   // chain block 0's Gibbs workgroups, iterations < 8 of the launch:
-                    // stamps[1024 + 4*4096 + ((t - i0) * 16 + 12 + q) * 4 + k]
-#define NMC_GSTAMP(k)                                                                        \
-  do {                                                                                       \
-    if (d.stamps && hcb == 0 && q < 4 && t - i0 < 8 && threadIdx.x == 0)                      \
-      d.stamps[1024 + 4 * 4096 + ((t - i0) * 16 + 12 + q) * 4 + (k)] = __builtin_amdgcn_s_memtime(); \
-  } while (0)
-#else
-#define NMC_GSTAMP(k) do {} while (0)
-#endif
-  for (int t = i0; t < i1; ++t) {
-    A = nmc_sweep_args_at<Fam>();
-    NMC_GSTAMP(3);
-    if (GW > 0 && t == i0) {   // (Dev.gsep: the first task starts this workgroup, or the
-                               //  likelihood workgroups have taken the launch over)
-      if (threadIdx.x < 64) {
-        const int r = nmc_grole_first_wait(d, hcb, q, (unsigned)d.G);
-        if (threadIdx.x == 0) lds[H.flag * 64] = r ? 1.0 : 0.0;
-      }
-      __syncthreads();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-      if (lds[H.flag * 64] == 0.0) break;
-    } else if (!nmc_wait_published(d, hcb, q, (unsigned)d.G * (unsigned)(t - i0 + 1), lds, H)) {
-      break;
-    }
-    NMC_GSTAMP(0);
-    if (w == 0) {   // the task's variates and sqrt(s2 / G) of the previous update
-      nmc_d2 hv;
-      if (d.zin) {
-        hv = nmc_sweep_hyper_variate(d.rhz, d.rhu, d.replay_n, d.rng_mode, d.P, d.C,
-                                     (uint32_t)(d.chain_base + cc), d.seed, d.ha, d.hlga, t, q,
-                                     cc);
-      } else {
-        const size_t hvi = (((size_t)(t - d.vbase) * d.P + q) * d.C + cc) * 2;
-        hv.a = d.vh[hvi];
-        hv.b = d.vh[hvi + 1];
-      }
-      lds[H.hv * 64 + (q * 64 + lane) * 2] = hv.a;
-      lds[H.hv * 64 + (q * 64 + lane) * 2 + 1] = hv.b;
-      hy[(NMC_HY_SDM * d.P + q) * 64] = sqrt(hy[(NMC_HY_S2 * d.P + q) * 64] / d.G);
-    }
-    __syncthreads();
-    // HyperParameter.update (:463-498) for the chain block, written through to the global
-    // slot of t (and the sample row); wave 0 stored it and counts it ready
-#ifdef NMC_STAMPS   // the update's phases (entry 14 + q): pass 1, mean, pass 2
-    {
-      const double* src = (t & 1) ? d.vb1 : d.vb0;
-      auto gs2 = [&](int k) {
-        if (d.stamps && hcb == 0 && q < 2 && t - i0 < 8 && threadIdx.x == 0)
-          d.stamps[1024 + 4 * 4096 + ((t - i0) * 16 + 14 + q) * 4 + k] = __builtin_amdgcn_s_memtime();
-      };
-      nmc_hyper_streams<NMC_SRC_SC1, false, 4>(d, src, cc, lds, H, q);
-      __syncthreads();
-      gs2(0);
-      if (w == 0) {
-        const double tot = nmc_hyper_combine(d, lds, H, q, lane);
-        const double sdm = lds[(H.hyp + NMC_HY_SDM * P + q) * 64 + lane];
-        const double hz = lds[H.hv * 64 + (q * 64 + lane) * 2];
-        lds[(H.hyp + NMC_HY_MU * P + q) * 64 + lane] = tot / G + sdm * hz;
-      }
-      __syncthreads();
-      gs2(1);
-      nmc_hyper_streams<NMC_SRC_SC1, true, 4>(d, src, cc, lds, H, q);
-      __syncthreads();
-      gs2(2);
-      // (diagnostics only: the full update below runs on the same inputs)
-    }
-#endif
-    if (GW > 0 && d.nleaf * (8 + (d.ntail ? 1 : 0)) <= 16)   // every stream in one round
-      nmc_hyper_once<GW == 8 ? 2 : 4>(d, (t & 1) ? d.vb1 : d.vb0, hcb, t, lds, H, q);
-    else
-      nmc_hyper<NMC_SRC_SC1, GW == 8 ? 1 : 4, true>(d, (t & 1) ? d.vb1 : d.vb0, hcb, t, lds, H,
-                                                    true, q);
-    NMC_GSTAMP(1);
-    if (w == 0) {
-      nmc_drain_vm();
-      if (lane == 0)
-        __hip_atomic_fetch_add(nmc_hrd(d, hcb, q), 1u, __ATOMIC_RELAXED,
-                               __HIP_MEMORY_SCOPE_AGENT);
-    }
-    NMC_GSTAMP(2);
-  }
-#undef NMC_GSTAMP
-  nmc_drain_vm();
-#undef d
-}
-
-// Dev.gsep: the Gibbs workgroups of SYNC_OWN as a kernel of their own (RB * P workgroups
-// of four waves, the small nmc_lds carve), launched on a second stream beside
-// nmc_k_sweep's RB * G likelihood workgroups: co-resident with two 61-KB likelihood
-// workgroups per CU where one kernel with a single LDS size would not be.
-// GW: its waves (4: four streams per wave, every stream of a 256-group update in one round)
-template <class Fam, int GW>
-__global__ void __launch_bounds__(64 * GW) nmc_k_sweep_gibbs(nmc_sweep_args<Fam> a_arg) {
-  (void)a_arg;
-  extern __shared__ __attribute__((aligned(16))) double lds[];
-  // (its waves share a CU with two likelihood workgroups: issue ahead of their tile waves,
-  //  the update is on every step's critical path; NMC_NOPRIO bit 2 drops it)
-  if (!(a_arg.d.noprio & 2)) __builtin_amdgcn_s_setprio(3);
-  nmc_sweep_gibbs_wg<Fam, GW>((int)blockIdx.x, lds);
-}
-
-template <class Fam, int MODE>
+template <class Fam>
 __global__ void __launch_bounds__(NMC_SWEEP_THREADS)
 nmc_k_sweep(nmc_sweep_args<Fam> a_arg) {
   (void)a_arg;   // (read through nmc_sweep_args_at(): the same bytes)
-  constexpr bool OWN = MODE == NMC_MODE_SYNC_OWN;
-  constexpr bool PARTIAL = MODE == NMC_MODE_SYNC_REG || MODE == NMC_MODE_SYNC_LDS || OWN;
-  constexpr bool HREG = MODE == NMC_MODE_SYNC_REG;
-  constexpr bool HALF = MODE == NMC_MODE_HALF;
   constexpr int NF = Fam::NFIELDS;
   constexpr int MP = Fam::MAXP;
-  static_assert(MODE == NMC_MODE_NOPOOL || MODE == NMC_MODE_HALF || PARTIAL, "sweep modes");
-  (void)OWN;
   extern __shared__ __attribute__((aligned(16))) double lds[];
   const nmc_sweep_args<Fam>* A = nmc_sweep_args_at<Fam>();
 #define d (A->d)
@@ -577,21 +166,23 @@ nmc_k_sweep(nmc_sweep_args<Fam> a_arg) {
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int W = blockDim.x >> 6;
   const int i0 = A->i0, i1 = A->i1;
+  // the queue waves: all but the control and the Gibbs wave (computed where it is used)
+  auto nqueue = [&]() { return W - 2; };
 
-  // ---- SYNC_OWN: the Gibbs workgroups (blocks RB * G .., unless Dev.gsep puts them in
-  //      their own kernel, nmc_k_sweep_gibbs) ----
-  if constexpr (OWN) if (!d.gsep && (int)blockIdx.x >= d.RB * d.G) {
+  // ---- the Gibbs workgroups (blocks RB * G .., unless Dev.gsep puts them in their own
+  //      kernel, nmc_k_sweep_gibbs) ----
+  if (!d.gsep && (int)blockIdx.x >= d.RB * d.G) {
     nmc_sweep_gibbs_wg<Fam, 0>((int)blockIdx.x - d.RB * d.G, lds);
     return;
   }
 
   // (Dev.cb0: the first chain block of this launch -- resident batches of chain blocks)
   const int g = blockIdx.x % d.G, cb = d.cb0 + (int)blockIdx.x / d.G;
-  const int c = HALF ? cb * 32 + (lane & 31) : cb * 64 + lane;
-  const bool live = c < d.C && (!HALF || lane < 32);   // writes this lane's outputs
+  const int c = cb * 64 + lane;
+  const bool live = c < d.C;                            // writes this lane's outputs
   const int cc = c < d.C ? c : d.C - 1;
   const bool ctl = w == 0;
-  const bool gw = PARTIAL && w == 1;                    // the Gibbs wave
+  const bool gw = w == 1;                               // the Gibbs wave
   const bool g0w = g == 0;                              // writes the chain block's hyper state
   // Everything else is re-derived from the laundered arguments where a step needs it, so the
   // persistent loop holds few values in registers: the step's view of the problem.
@@ -608,7 +199,7 @@ nmc_k_sweep(nmc_sweep_args<Fam> a_arg) {
     if (pro) {
       v.P = d.P; v.G = d.G; v.C = d.C;
       v.ngrp = (int)(d.off[g + 1] - d.off[g]);
-      v.L = nmc_sweep_lds(Fam::NACC, v.P, PARTIAL, MODE == NMC_MODE_SYNC_LDS, v.G, d.nmax * NF);
+      v.L = nmc_sweep_lds(Fam::NACC, v.P, d.nmax * NF);
       v.TI = nmc_tiles(v.ngrp, d.tile);
     } else {
       int k[NMC_SWK_COUNT];
@@ -619,7 +210,7 @@ nmc_k_sweep(nmc_sweep_args<Fam> a_arg) {
       v.TI.n = k[NMC_SWK_N]; v.TI.nt = k[NMC_SWK_NT]; v.TI.h = k[NMC_SWK_H];
       v.TI.a = k[NMC_SWK_A]; v.TI.b = k[NMC_SWK_B];
       v.L.th = k[NMC_SWK_TH]; v.L.part = k[NMC_SWK_PART]; v.L.st = k[NMC_SWK_ST];
-      v.L.hyp = k[NMC_SWK_HYP]; v.L.hval = k[NMC_SWK_HVAL]; v.L.zl = k[NMC_SWK_ZL];
+      v.L.hyp = k[NMC_SWK_HYP]; v.L.zl = k[NMC_SWK_ZL];
       v.L.zm = k[NMC_SWK_ZM]; v.L.cw = k[NMC_SWK_CW]; v.L.flag = k[NMC_SWK_FLAG];
       v.L.rows = k[NMC_SWK_ROWS]; v.L.total = k[NMC_SWK_TOTAL];
     }
@@ -628,19 +219,6 @@ nmc_k_sweep(nmc_sweep_args<Fam> a_arg) {
     v.gc = (size_t)g * v.C + cc;
     return v;
   };
-  auto hl_view = [](const nmc_sweep_layout& L) {   // the Gibbs helpers' view of the carve
-    nmc_lds_layout H;
-    H.hval = L.hval;
-    H.hyp = L.hyp;
-    H.flag = L.flag;
-    return H;
-  };
-  // the task this workgroup closes after the loop: ge-lag+g (groups 0 .. lag-1), -1: none
-  auto close_task = [&](const View& v) {
-    const int k0 = v.ge - v.lag > v.gs0 ? v.ge - v.lag : v.gs0;
-    return PARTIAL && !OWN && k0 + g < v.ge ? k0 + g : -1;
-  };
-  // {z, log u} of step (tn, pn) -> LDS slot `slot` (this lane's chain)
   // {z, log u} of step (tn, pn) -> LDS slot `slot`: part j of the draw (Dev.zin; j = 3: all
   // three), or the LDS-DMA of the pair nmc_k_fill wrote to the ring vzl (the issuing wave
   // drains its vmcnt before the next barrier; zm holds 1.0)
@@ -694,7 +272,7 @@ nmc_k_sweep(nmc_sweep_args<Fam> a_arg) {
       st[(NMC_ST_NA * P + p) * 64] = (double)d.nacc[ip];
       st[(NMC_ST_NR * P + p) * 64] = (double)d.nrej[ip];
       st[(NMC_ST_TA * P + p) * 64] = (double)d.tacc[ip];
-      if (PARTIAL) {   // hyper-parameters after iteration i0-1 (slot (i0-1) & 1)
+      {   // hyper-parameters after iteration i0-1 (slot (i0-1) & 1)
         const size_t ho = nmc_hslot(d, i0 - 1) + (size_t)p * C + cc;
         const double s2 = d.s2[ho];
         hy[(NMC_HY_MU * P + p) * 64] = d.mu[ho];
@@ -714,7 +292,7 @@ nmc_k_sweep(nmc_sweep_args<Fam> a_arg) {
           lds[(L.part + j * NMC_NSLOT + k) * 64 + lane] = -0.0;
       lds[L.flag * 64 + lane] = 0.0;
       if (lane < 2)   // both tile queues: the first nq entries go by rank
-        ((unsigned*)(lds + L.flag * 64 + 4))[lane] = (unsigned)(W - 1 - (PARTIAL ? 1 : 0));
+        ((unsigned*)(lds + L.flag * 64 + 4))[lane] = (unsigned)nqueue();
       if (lane == 0) {                     // the step constants (view())
         int* kw = (int*)lds + NMC_SWK_AT;
         kw[NMC_SWK_P] = v.P; kw[NMC_SWK_G] = v.G; kw[NMC_SWK_C] = v.C;
@@ -722,7 +300,7 @@ nmc_k_sweep(nmc_sweep_args<Fam> a_arg) {
         kw[NMC_SWK_N] = v.TI.n; kw[NMC_SWK_NT] = v.TI.nt; kw[NMC_SWK_H] = v.TI.h;
         kw[NMC_SWK_A] = v.TI.a; kw[NMC_SWK_B] = v.TI.b;
         kw[NMC_SWK_TH] = L.th; kw[NMC_SWK_PART] = L.part; kw[NMC_SWK_ST] = L.st;
-        kw[NMC_SWK_HYP] = L.hyp; kw[NMC_SWK_HVAL] = L.hval; kw[NMC_SWK_ZL] = L.zl;
+        kw[NMC_SWK_HYP] = L.hyp; kw[NMC_SWK_RSV] = L.zl; kw[NMC_SWK_ZL] = L.zl;
         kw[NMC_SWK_ZM] = L.zm; kw[NMC_SWK_CW] = L.cw; kw[NMC_SWK_FLAG] = L.flag;
         kw[NMC_SWK_ROWS] = L.rows; kw[NMC_SWK_TOTAL] = L.total;
       }
@@ -753,14 +331,14 @@ nmc_k_sweep(nmc_sweep_args<Fam> a_arg) {
         const typename Fam::Reg reg = fam.prepare(thp);
         // quad rows ({x, y}, rows.h nmc_ll_rows_lds_quad): intercept and slope of the four
         // chains of this lane's quarter position
-        const bool quad = Fam::ASM_ROWS && !HALF && d.quad;
+        const bool quad = Fam::ASM_ROWS && d.quad;
         double q4c[4], q4d[4];
-        if constexpr (Fam::ASM_ROWS && !HALF) if (quad) {
+        if constexpr (Fam::ASM_ROWS) if (quad) {
           nmc_quarters(reg.b0, q4c);
           nmc_quarters(reg.b[0], q4d);
         }
         typename Fam::Reg preg = reg;   // paired rows: the partner lane's (lane ^ 32) values
-        if constexpr (nmc_paired_rows_ok<Fam>() && !HALF) if (d.paired && !quad) {
+        if constexpr (nmc_paired_rows_ok<Fam>()) if (d.paired && !quad) {
           const bool hi = lane >= 32;
 #pragma unroll
           for (int q = 0; q < MP; ++q) {
@@ -782,7 +360,7 @@ nmc_k_sweep(nmc_sweep_args<Fam> a_arg) {
         // partial slot is fixed: the sums stay in order.
         const int ne = nt + zj;
         unsigned* qc = tcnt + sp;
-        const int nq = W - 1 - (PARTIAL ? 1 : 0);
+        const int nq = nqueue();
         auto issue = [&]() -> unsigned {   // lane 0: a take
           return lane == 0 ? __hip_atomic_fetch_add(qc, 1u, __ATOMIC_RELAXED,
                                                     __HIP_MEMORY_SCOPE_WORKGROUP)
@@ -803,7 +381,7 @@ nmc_k_sweep(nmc_sweep_args<Fam> a_arg) {
                                        : 0u;
           return ne - (int)__builtin_amdgcn_readlane(i, 0) > nq ? resolve(issue()) : -1;
         };
-        const int rank = w - 1 - (PARTIAL ? 1 : 0);   // (control: -1)
+        const int rank = w - 2;   // (of a queue wave)
         NMC_RS_STAMP((t - i0) * P + p, 2);
         int kq = cpick ? ctake() : role != 0 ? resolve(issue()) : (rank < ne ? rank : -1);
         NMC_RS_STAMP((t - i0) * P + p, 3);
@@ -825,12 +403,12 @@ nmc_k_sweep(nmc_sweep_args<Fam> a_arg) {
             const int ra = v.TI.start(k), rn = v.TI.len(k);
             double acc[Fam::NACC];
             bool done = false;
-            if constexpr (Fam::ASM_ROWS && !HALF) if (quad) {
+            if constexpr (Fam::ASM_ROWS) if (quad) {
               nmc_ll_rows_lds_quad(fam, reg, lrows + (size_t)ra * NF, rn, acc, q4c, q4d);
               done = true;
             }
-            if constexpr (nmc_paired_rows_ok<Fam>()) if (!done && (HALF || d.paired)) {
-              nmc_ll_rows_lds<Fam, true, HALF>(fam, reg, lrows + (size_t)ra * NF, rn, acc, &preg);
+            if constexpr (nmc_paired_rows_ok<Fam>()) if (!done && d.paired) {
+              nmc_ll_rows_lds<Fam, true, false>(fam, reg, lrows + (size_t)ra * NF, rn, acc, &preg);
               done = true;
             }
             if (!done) nmc_ll_rows_lds(fam, reg, lrows + (size_t)ra * NF, rn, acc);
@@ -849,17 +427,18 @@ nmc_k_sweep(nmc_sweep_args<Fam> a_arg) {
 
   bool ok = true;
   // ---- the Gibbs wave: its own loop, meeting the others at both barriers of every step ----
-  if constexpr (PARTIAL) if (gw) {
+  if (gw) {
     if (!(d.noprio & 1)) __builtin_amdgcn_s_setprio(3);
-    bool gfall = false;   // (SYNC_OWN, Dev.gsep: this launch's tasks are updated here)
-    // task k = (kt, kq): poll its publication, update (HyperParameter.update :463-498),
-    // write (the global slot of kt and the sample row); priors: this step's priors from the
-    // update (p, sp, t: the step); returns the poll's verdict
+    bool gfall = false;   // (Dev.gsep: this launch's tasks are updated here)
+    // task k = (kt, kq): wait for its ready count and read the four hyper values (or, in the
+    // Dev.gsep fallback, update it here: HyperParameter.update :463-498; write: the global slot
+    // of kt and the sample row); priors: this step's priors from the update (p, sp, t: the
+    // step); returns the poll's verdict
     auto task = [&](const View& v, int k, bool write, bool priors, int p, int sp, int t) -> bool {
-      const int P = v.P, G = v.G, C = v.C;
+      const int P = v.P, G = v.G;
       const nmc_sweep_layout& L = v.L;
       const int kq = k % P, kt = k / P;
-      if constexpr (OWN) {   // the Gibbs workgroup of (cb, kq) has counted task k ready
+      {   // the Gibbs workgroup of (cb, kq) has counted task k ready
         const unsigned target = (unsigned)(kt - i0 + 1) + d.pbase;
         if (!d.gsep) {
           if (!nmc_poll_count(d, nmc_hrd(d, cb, kq), target)) return false;
@@ -879,43 +458,10 @@ nmc_k_sweep(nmc_sweep_args<Fam> a_arg) {
                                      __HIP_MEMORY_SCOPE_AGENT);
           }
         }
-      } else {
-        if (!nmc_poll_published(d, cb, kq, (unsigned)G * (unsigned)(kt - i0 + 1))) return false;
       }
       // keep the payload loads below the poll (no instruction: wavefront scope)
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-      if constexpr (OWN) {
-        if (!gfall) nmc_hyper_read(d, kt, kq, cc, lds, L.hyp);
-      } else {
-        nmc_d2 hv;
-        if (d.zin) {
-          hv = nmc_sweep_hyper_variate(d.rhz, d.rhu, d.replay_n, d.rng_mode, P, C,
-                                       (uint32_t)(d.chain_base + cc), d.seed, d.ha, d.hlga, kt, kq,
-                                       cc);
-        } else {   // the fill kernel's pair
-          const size_t hvi = (((size_t)(kt - d.vbase) * P + kq) * C + cc) * 2;
-          hv.a = d.vh[hvi];
-          hv.b = d.vh[hvi + 1];
-        }
-        if constexpr (HREG) {
-          double xv[64];
-          const double* src = ((kt & 1) ? d.vb1 : d.vb0) + (size_t)kq * G * C + cc;
-#pragma unroll
-          for (int u = 0; u < 64; ++u) xv[u] = nmc_ldv<NMC_SRC_SC1>(src + (size_t)u * C);
-          nmc_hyper_compute_reg(d, cb, kt, kq, lds, L.hyp, write, hv.a, hv.b, xv);
-        } else {
-          const nmc_lds_layout H = hl_view(L);
-          const double* src = (kt & 1) ? d.vb1 : d.vb0;
-          if ((C & 1) == 0) {
-            nmc_hyper_dma(d, src, kq, cb, 0, G, lds, H, 0);
-            nmc_drain_vm();
-          } else {
-            nmc_hyper_load(d, src, kq, cc, 0, G, lds, H, 0);
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-          }
-          nmc_hyper_compute(d, cb, kt, kq, lds, H, write, hv.a, hv.b, 0);
-        }
-      }
+      if (!gfall) nmc_hyper_read(d, kt, kq, cc, lds, L.hyp);
       if (priors) {   // the update lands in the step that needs it: this step's priors
         const double* th = lds + L.th * 64 + lane;
         const double* st = lds + L.st * 64 + lane;
@@ -957,20 +503,12 @@ nmc_k_sweep(nmc_sweep_args<Fam> a_arg) {
         nmc_step_barrier();   // B
       }
     }
-    // closing: task close_k (the matching barrier of the other waves' nmc_wait_published)
     A = nmc_sweep_args_at<Fam>();
     const View v = view();
-    const int close_k = close_task(v);
-    if (ok && close_k >= 0) {
-      if (nmc_wait_published(d, cb, close_k % v.P,
-                             (unsigned)v.G * (unsigned)(close_k / v.P - i0 + 1), lds,
-                             hl_view(v.L)))
-        task(v, close_k, true, false, 0, 0, 0);
-    }
-    // SYNC_OWN, Dev.gsep: group 0's wave sees the launch's last tasks done -- by the Gibbs
+    // Dev.gsep: group 0's wave sees the launch's last tasks done -- by the Gibbs
     // kernel (ready counts), or by itself when nobody started them (the fallback; also when
     // the launch is too short for any task to fall due in the loop)
-    if constexpr (OWN) if (ok && d.gsep && g0w) {
+    if (ok && d.gsep && g0w) {
       for (int k = v.ge - v.lag > v.gs0 ? v.ge - v.lag : v.gs0; k < v.ge && ok; ++k)
         ok = task(v, k, true, false, 0, 0, 0);
     }
@@ -1006,7 +544,7 @@ nmc_k_sweep(nmc_sweep_args<Fam> a_arg) {
     if (live) {
       const int row = nmc_record_row(d, tq);
       if (row >= 0) {
-        const int col = q * (G + (PARTIAL ? 2 : 0)) + (PARTIAL ? 2 : 0) + g;
+        const int col = q * (G + 2) + 2 + g;
         d.samples[((size_t)row * d.cols + col) * C + c] = th[q * 64];
       }
       if (tq < d.trace_n) {
@@ -1047,7 +585,7 @@ nmc_k_sweep(nmc_sweep_args<Fam> a_arg) {
       (void)G; (void)C; (void)tcnt;   // (not every instance uses them)
       const Fam& fam = A->fam;
       const int gs = t * P + p, sp = gs & 1;
-      const bool due = PARTIAL && gs - v.lag >= v.gs0;   // the Gibbs wave has a task this step
+      const bool due = gs - v.lag >= v.gs0;              // the Gibbs wave has a task this step
       const bool post_prior = due && P <= 2;             // ... whose update this step's prior needs
       // ---- control: the pending update of step gs-1 and this step's decision operands:
       //      the proposal, both outcomes of the counters and of the (tuned) scale, priors ----
@@ -1088,15 +626,10 @@ nmc_k_sweep(nmc_sweep_args<Fam> a_arg) {
         cwv[NMC_CW_NRR * 64] = nrR;
         cwv[NMC_CW_TA * 64] = st[(NMC_ST_TA * P + p) * 64];
         if (!post_prior) {   // priors (:293-294)
-          if constexpr (PARTIAL) {
-            const double m = hy[(NMC_HY_MU * P + p) * 64], sd = hy[(NMC_HY_SD * P + p) * 64];
-            const double lsd = hy[(NMC_HY_LSD * P + p) * 64], isd = hy[(NMC_HY_ISD * P + p) * 64];
-            c_lpc = t > 0 ? nmc_norm_logpdf_r(c_v, m, sd, isd, lsd) : st[(NMC_ST_LP * P + p) * 64];
-            c_lpp = nmc_norm_logpdf_r(c_prop, m, sd, isd, lsd);
-          } else {
-            c_lpc = st[(NMC_ST_LP * P + p) * 64];
-            c_lpp = nmc_sweep_prior(d.pfam[p], d.ppar + 8 * p, c_prop);
-          }
+          const double m = hy[(NMC_HY_MU * P + p) * 64], sd = hy[(NMC_HY_SD * P + p) * 64];
+          const double lsd = hy[(NMC_HY_LSD * P + p) * 64], isd = hy[(NMC_HY_ISD * P + p) * 64];
+          c_lpc = t > 0 ? nmc_norm_logpdf_r(c_v, m, sd, isd, lsd) : st[(NMC_ST_LP * P + p) * 64];
+          c_lpp = nmc_norm_logpdf_r(c_prop, m, sd, isd, lsd);
         }
       }
 
@@ -1104,7 +637,7 @@ nmc_k_sweep(nmc_sweep_args<Fam> a_arg) {
       // ---- every wave: the likelihood of the proposal (:615-635), tile by tile from the
       //      step's LDS queue; entry 0 (when there is a next step) draws its variates ----
       run_tiles(v, t, p, ctl ? 1 : 0, [&]() {
-        if constexpr (PARTIAL) if (ctl) count_published();
+        if (ctl) count_published();
       });
       if (p == 0) NMC_STAMP(t, 9);
       if (ctl) nmc_drain_vm();   // (its variate DMA has landed)
@@ -1133,7 +666,7 @@ nmc_k_sweep(nmc_sweep_args<Fam> a_arg) {
       if (ctl) {
         // every entry is taken; the queue is reused at step gs + 2 (its first nq entries
         // by rank)
-        if (lane == 0) tcnt[sp] = (unsigned)(W - 1 - (PARTIAL ? 1 : 0));
+        if (lane == 0) tcnt[sp] = (unsigned)nqueue();
         if (post_prior) {   // the Gibbs wave evaluated this step's priors (read in the slot
                             // sums' LDS round trip)
           c_lpc = cwv[NMC_CW_LPC * 64];
@@ -1155,12 +688,11 @@ nmc_k_sweep(nmc_sweep_args<Fam> a_arg) {
         // :369-383, :608-610 (+ tune :385-437, prepared above)
         const double vn = accept ? c_prop : c_v;
         th[p * 64] = vn;
-        if constexpr (PARTIAL) {   // publish write-through; counted at the next step's start
-          if (live)
-            __hip_atomic_store(((t & 1) ? d.vb1 : d.vb0) + (size_t)p * G * C + v.gc, vn,
-                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          pub_p = p;
-        }
+        // publish write-through; counted at the next step's start
+        if (live)
+          __hip_atomic_store(((t & 1) ? d.vb1 : d.vb0) + (size_t)p * G * C + v.gc, vn,
+                             __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        pub_p = p;
         st[(NMC_ST_S * P + p) * 64] = accept ? c_sA : c_sR;
         q_acc = accept;
         q_plp = accept ? c_lpp : c_lpc;
@@ -1185,18 +717,15 @@ nmc_k_sweep(nmc_sweep_args<Fam> a_arg) {
   A = nmc_sweep_args_at<Fam>();
   const View v = view();
   if (ctl) {
-    if constexpr (PARTIAL) count_published();   // the last parameter's count
+    count_published();   // the last parameter's count
     if (pend_p >= 0) apply_pending(v);
   }
-  // ---- epilogue: state back to HBM (control wave) ----
+  // ---- epilogue: state back to HBM (control wave; the values went out write-through) ----
   if (ctl && live && ok) {
     const int P = v.P, G = v.G, C = v.C;
-    const double* th = lds + v.L.th * 64 + lane;
     const double* st = lds + v.L.st * 64 + lane;
-    double* vo = ((i1 - 1) & 1) ? d.vb1 : d.vb0;
     for (int p = 0; p < P; ++p) {
       const size_t ip = (size_t)p * G * C + v.gc;
-      if (!PARTIAL) vo[ip] = th[p * 64];   // (partial pooling: published write-through)
       d.lp[ip] = st[(NMC_ST_LP * P + p) * 64];
       d.scale[ip] = st[(NMC_ST_S * P + p) * 64];
       d.nacc[ip] = (int)st[(NMC_ST_NA * P + p) * 64];
@@ -1204,14 +733,6 @@ nmc_k_sweep(nmc_sweep_args<Fam> a_arg) {
       d.tacc[ip] = (long long)st[(NMC_ST_TA * P + p) * 64];
     }
     d.ll[v.gc] = c_LL;
-  }
-  // ---- closing Gibbs task (partial pooling): the Gibbs wave computes it; this is the
-  //      matching barrier of its nmc_wait_published ----
-  if constexpr (PARTIAL) {
-    const int close_k = close_task(v);
-    if (ok && close_k >= 0)
-      nmc_wait_published(d, cb, close_k % v.P, (unsigned)v.G * (unsigned)(close_k / v.P - i0 + 1),
-                         lds, hl_view(v.L));
   }
   nmc_drain_vm();
   NMC_RUN_SL(3);

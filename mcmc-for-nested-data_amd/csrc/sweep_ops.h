@@ -7,17 +7,16 @@
 #include "ctx.h"
 #include "fam_make.h"
 
-// The sweep kernel instance of a mode (for launches and occupancy queries): SYNC_OWN only
-// (partial pooling over G > 128 groups, nestmc.hip choose_geometry)
+// The sweep kernel instance (for launches and occupancy queries)
 template <class Fam>
-static const void* nmc_sweep_kernel(int mode) {
-  return mode == NMC_MODE_SYNC_OWN ? (const void*)nmc_k_sweep<Fam, NMC_MODE_SYNC_OWN> : nullptr;
+static const void* nmc_sweep_kernel() {
+  return (const void*)nmc_k_sweep<Fam>;
 }
 
 // (four waves: an eight-wave form with two streams per wave needs <= 88 VGPRs to sit beside
 //  two likelihood workgroups and spilled at that budget)
 template <class Fam>
-static const void* nmc_sweep_gibbs_kernel(int) {
+static const void* nmc_sweep_gibbs_kernel() {
   return (const void*)nmc_k_sweep_gibbs<Fam, 4>;
 }
 
@@ -27,11 +26,11 @@ static int nmc_sweep_call_t(nmc_ctx* x, const Fam& fam, NmcCall& c) {
   switch (c.op) {
     case NMC_OP_RUN: {
       const int i0 = c.i0, i1 = c.i1;
-      return nmc_run_launches(x, i0, i1, [&](int mode, const Dev& d, dim3 grid, dim3 block,
+      return nmc_run_launches(x, i0, i1, [&](int, const Dev& d, dim3 grid, dim3 block,
                                              size_t lds) {
         nmc_sweep_args<Fam> a{d, fam, i0, i1};
         void* args[] = {&a};
-        if (mode == NMC_MODE_SYNC_OWN && d.gsep) {
+        if (d.gsep) {
           // the Gibbs workgroups' kernel on the second stream, forked after the work before
           // this launch and joined before the work after it; both kernels resident together
           // (NMC_OP_CAN_PERSIST), each waiting on counters the other advances -- and, when
@@ -41,27 +40,27 @@ static int nmc_sweep_call_t(nmc_ctx* x, const Fam& fam, NmcCall& c) {
           a.d.gep = x->gepoch;
           const unsigned nb = grid.x / (unsigned)d.G;   // chain blocks of this launch
           auto gibbs = [&](hipStream_t s) {
-            hipLaunchKernel(nmc_sweep_gibbs_kernel<Fam>(d.gwaves), dim3(nb * d.P),
+            hipLaunchKernel(nmc_sweep_gibbs_kernel<Fam>(), dim3(nb * d.P),
                             dim3(64 * d.gwaves), args, sweep_gibbs_lds_bytes(x), s);
           };
           if (x->gserial) {   // (tests: both kernels on one stream, serialized; 1: the Gibbs
                               //  kernel first, 2: after the likelihood kernel)
             if (x->gserial == 1) gibbs(x->stream);
-            hipLaunchKernel(nmc_sweep_kernel<Fam>(mode), grid, block, args, lds, x->stream);
+            hipLaunchKernel(nmc_sweep_kernel<Fam>(), grid, block, args, lds, x->stream);
             if (x->gserial == 2) gibbs(x->stream);
             return;
           }
           hipEventRecord(x->gev[0], x->stream);
           hipStreamWaitEvent(x->gstream, x->gev[0], 0);
           gibbs(x->gstream);
-          hipLaunchKernel(nmc_sweep_kernel<Fam>(mode), grid, block, args, lds, x->stream);
+          hipLaunchKernel(nmc_sweep_kernel<Fam>(), grid, block, args, lds, x->stream);
           hipEventRecord(x->gev[1], x->gstream);
           hipStreamWaitEvent(x->stream, x->gev[1], 0);
           return;
         }
-        // (SYNC_OWN: the Gibbs workgroups after the likelihood ones)
-        const dim3 gr(mode == NMC_MODE_SYNC_OWN ? (unsigned)sweep_grid(x) : grid.x);
-        hipLaunchKernel(nmc_sweep_kernel<Fam>(mode), gr, block, args, lds, x->stream);
+        // (one grid: the Gibbs workgroups after the likelihood ones)
+        hipLaunchKernel(nmc_sweep_kernel<Fam>(), dim3((unsigned)sweep_grid(x)), block, args, lds,
+                        x->stream);
       });
     }
     case NMC_OP_CAN_PERSIST: {   // may every workgroup of the grid be resident at once?
@@ -69,19 +68,16 @@ static int nmc_sweep_call_t(nmc_ctx* x, const Fam& fam, NmcCall& c) {
         c.result = f;
         return 0;
       }
-      int nb = 0;
-      c.result = 0;
-      const void* k = nmc_sweep_kernel<Fam>(nmc_persist_mode(x));
-      if (k && hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, 64 * x->d.W,
-                                                            nmc_persist_lds(x)) == hipSuccess)
-        c.result = sweep_grid(x) <= (int64_t)nmc_safe_blocks(x, nb) * x->ncu;
-      if (x->d.gsep && k) {
+      const void* k = nmc_sweep_kernel<Fam>();
+      const int64_t cap = nmc_resident_wgs(x, k, nmc_persist_lds(x));   // (-1: holds no grid)
+      c.result = sweep_grid(x) <= cap;
+      if (x->d.gsep) {
         // the largest batch of chain blocks whose likelihood workgroups are co-resident and
         // leave, on the CUs holding the most of them, the LDS and the wave slots (<= 168
         // VGPRs: three waves per SIMD) for one four-wave Gibbs workgroup; the launches run
         // the chain blocks in such batches (nmc_run_launches)
         int ng = 0;
-        const void* gk = nmc_sweep_gibbs_kernel<Fam>(x->d.gwaves);
+        const void* gk = nmc_sweep_gibbs_kernel<Fam>();
         const int gw = x->d.gwaves;
         hipFuncAttributes am{}, ag{};
         const bool gok = hipOccupancyMaxActiveBlocksPerMultiprocessor(
@@ -90,7 +86,6 @@ static int nmc_sweep_call_t(nmc_ctx* x, const Fam& fam, NmcCall& c) {
                          hipFuncGetAttributes(&ag, gk) == hipSuccess;
         // VGPRs per SIMD (512 per lane, allocated in 8s) and wave slots (8 per SIMD)
         auto vg = [](int r) { return (r + 7) / 8 * 8; };
-        const int64_t cap = (int64_t)nmc_safe_blocks(x, nb) * x->ncu;
         int best = 0;
         for (int b = 1; gok && b <= x->d.RB; ++b) {
           const int64_t wg = (int64_t)b * x->d.G;
@@ -107,12 +102,9 @@ static int nmc_sweep_call_t(nmc_ctx* x, const Fam& fam, NmcCall& c) {
       return 0;
     }
     case NMC_OP_CAPACITY: {
-      int nb = 0;
-      const void* k = nmc_sweep_kernel<Fam>(run_mode(x));
-      if (!k || hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, 64 * x->d.W,
-                                                             run_lds_bytes(x)) != hipSuccess)
-        return nmc_fail(-2, "occupancy query failed");
-      c.result = nmc_safe_blocks(x, nb) * x->ncu;
+      const int64_t n = nmc_resident_wgs(x, nmc_sweep_kernel<Fam>(), run_lds_bytes(x));
+      if (n < 0) return nmc_fail(-2, "occupancy query failed");
+      c.result = (int)n;
       return 0;
     }
   }

@@ -70,6 +70,7 @@ def test_max_over_ranks_two_processes():
     ("nmc_k_run<FamLinreg<2>, NMC_MODE_SYNC_REG, true>", "FamLinreg<2>"),
     ("nmc_k_sweep<FamGaussMean<3>, NMC_MODE_HALF>", "FamGaussMean<3>"),
     ("nmc_k_run<FamUser, NMC_MODE_SYNC, false>", "FamUser"),
+    ("nmc_k_sweep<FamLinreg<2>, NMC_MODE_SYNC_OWN>", "FamLinreg<2>"),
 ])
 def test_family_instance_of_kernel_name(kernel, inst):
     """The roofline's per-row instruction count is keyed by the step kernel's family."""
