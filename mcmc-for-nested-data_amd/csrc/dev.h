@@ -207,7 +207,7 @@ __host__ __device__ inline nmc_lds_layout nmc_lds(int nacc, int P, int partial, 
   L.zl = L.hleaf + (partial ? P * nleaf : 0);
   L.hv = L.zl + 4;
   L.cw = L.hv + (partial ? 2 * P : 0);
-  L.flag = L.cw + 8;    // (NMC_CW_* uses 7 columns)
+  L.flag = L.cw + 8;    // (NMC_CW_* uses all 8 columns)
   L.xchg = L.flag + 1;
   L.rows = L.xchg;
   // (+1 column: the pipelined likelihood loop prefetches one block past a wave's rows)
@@ -217,8 +217,10 @@ __host__ __device__ inline nmc_lds_layout nmc_lds(int nacc, int P, int partial, 
 enum { NMC_ST_S = 0, NMC_ST_LP, NMC_ST_NA, NMC_ST_NR, NMC_ST_TA };
 enum { NMC_HY_MU = 0, NMC_HY_SD, NMC_HY_LSD, NMC_HY_S2, NMC_HY_SDM, NMC_HY_ISD };
 // control-wave columns of the LDS carve (cw): LPC/LPP: priors of the step made by the
-// Gibbs wave; NAA..TA: counter outcomes of the decided step
-enum { NMC_CW_LPC = 0, NMC_CW_LPP, NMC_CW_NAA, NMC_CW_NRA, NMC_CW_NAR, NMC_CW_NRR, NMC_CW_TA };
+// Gibbs wave; NAA..TA: counter outcomes of the decided step; PN: the next step's proposal
+// (nmc_k_run's restart without gathers: written between the step's barriers A and B)
+enum { NMC_CW_LPC = 0, NMC_CW_LPP, NMC_CW_NAA, NMC_CW_NRA, NMC_CW_NAR, NMC_CW_NRR, NMC_CW_TA,
+       NMC_CW_PN };
 
 // Chunk k of nchunks of [r0, r1) (contiguous, balanced).
 __device__ __forceinline__ void nmc_chunk(int64_t r0, int64_t r1, int k, int nchunks,

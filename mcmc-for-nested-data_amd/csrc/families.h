@@ -59,6 +59,12 @@ struct FamLinreg {
     r.sig = sigma_known > 0.0 ? sigma_known : (intercept ? th[K + 1] : th[K]);
     return r;
   }
+  // the parameters prepare() copies into b0 and b[0] (ib0 < 0: b0 is the constant 0.0): the
+  // quad rows' restart reads them per chain slot straight from the parameters' LDS columns
+  __device__ __forceinline__ void quad_params(int& ib0, int& ib) const {
+    ib0 = intercept ? 0 : -1;
+    ib = intercept ? 1 : 0;
+  }
   // residual e = (b0 - y) + sum_j x_j b_j, accumulated with fmas from the intercept side
   // (every likelihood path -- LDS asm loop, pair loop, scalar loop -- forms the same e)
   __device__ __forceinline__ void accum(const Reg& r, const double* __restrict__ row,

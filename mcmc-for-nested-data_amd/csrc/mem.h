@@ -35,6 +35,36 @@ __device__ __forceinline__ void nmc_store_wt(double* p, double v) {
   asm volatile("global_store_dwordx2 %0, %1, off sc1" ::"v"(p), "v"(v) : "memory");
 }
 
+// The step's tile grab: lane 0 adds 1 to the LDS counter at ctr, the value before in lane 0 of
+// the result (call with the whole wave; the other lanes' results are undefined).  Written as
+// the instruction because the compiler orders every LDS access of a wave that also issues
+// LDS-DMA behind that wave's outstanding global memory (s_waitcnt vmcnt(0) in front of
+// the __hip_atomic_fetch_add's ds_add_rtn_u32): the tile counters are never a DMA target, and
+// on the control wave that wait stood for the variate DMA, the sample / trace stores and the
+// publish count before every tile.  The compiler does not know of the return in flight either:
+// nmc_lds_grab_value waits for it (lgkmcnt) and hands out lane 0's value, and nothing else may
+// touch the result.
+__device__ __forceinline__ unsigned nmc_lds_grab(unsigned* ctr) {
+  const unsigned a = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned*)ctr;
+  const unsigned one = 1u;
+  unsigned r;
+  unsigned long long ex;
+  asm volatile(
+      "s_mov_b64 %[ex], exec\n\t"
+      "s_mov_b64 exec, 1\n\t"
+      "ds_add_rtn_u32 %[r], %[a], %[one]\n\t"
+      "s_mov_b64 exec, %[ex]"
+      : [r] "=&v"(r), [ex] "=&s"(ex)
+      : [a] "v"(a), [one] "v"(one)
+      : "memory");
+  return r;
+}
+__device__ __forceinline__ int nmc_lds_grab_value(unsigned r) {
+  int k;   // (the result is an input only: no tied copy of it in front of the wait)
+  asm volatile("s_waitcnt lgkmcnt(0)\n\tv_readlane_b32 %0, %1, 0" : "=s"(k) : "v"(r) : "memory");
+  return k;
+}
+
 // The calling wave polls the chain block's publish counter until it reaches target
 // (bounded; a timeout is recorded in d.tmo and reported by the host).  The counter is
 // sharded 8 ways (workgroup g adds to shard g % 8, each shard on its own 128-B line)

@@ -227,6 +227,38 @@ __device__ __forceinline__ void nmc_rows_lds_linreg2_paired(const double* p, int
 // a 16-row block from register set A (v[120:135]) / B (v[136:151]): its rows 4m+q, m = 0..3
 #define NMC_QBA NMC_QH(120, 122, 124, 126) NMC_QH(128, 130, 132, 134)
 #define NMC_QBB NMC_QH(136, 138, 140, 142) NMC_QH(144, 146, 148, 150)
+// the loop over nb 16-row blocks (shared by the two entries below)
+#define NMC_QLOOP                                  \
+      NMC_Q4(120, 0)                               \
+      "L_nmc_q_%=:\n"                              \
+      "s_sub_u32 %[cnt], %[cnt], 1\n"              \
+      "s_cmp_gt_i32 %[cnt], 0\n"                   \
+      "s_cbranch_scc0 L_nmc_qla_%=\n"              \
+      NMC_Q4(136, 256)                             \
+      "s_waitcnt lgkmcnt(4)\n"                     \
+      NMC_QBA                                      \
+      "v_add_u32 %[addr], 0x200, %[addr]\n"        \
+      "s_sub_u32 %[cnt], %[cnt], 1\n"              \
+      "s_cmp_gt_i32 %[cnt], 0\n"                   \
+      "s_cbranch_scc0 L_nmc_qlb_%=\n"              \
+      NMC_Q4(120, 0)                               \
+      "s_waitcnt lgkmcnt(4)\n"                     \
+      NMC_QBB                                      \
+      "s_branch L_nmc_q_%=\n"                      \
+      "L_nmc_qla_%=:\n"                            \
+      "s_waitcnt lgkmcnt(0)\n"                     \
+      NMC_QBA                                      \
+      "s_branch L_nmc_qend_%=\n"                   \
+      "L_nmc_qlb_%=:\n"                            \
+      "s_waitcnt lgkmcnt(0)\n"                     \
+      NMC_QBB                                      \
+      "L_nmc_qend_%=:\n"
+#define NMC_QCLOBBERS                                                                            \
+  "v120", "v121", "v122", "v123", "v124", "v125", "v126", "v127", "v128", "v129", "v130",       \
+      "v131", "v132", "v133", "v134", "v135", "v136", "v137", "v138", "v139", "v140", "v141",   \
+      "v142", "v143", "v144", "v145", "v146", "v147", "v148", "v149", "v150", "v151", "v152",   \
+      "v153", "v154", "v155", "v156", "v157", "v158", "v159", "v160", "v161", "v162", "v163",   \
+      "v164", "v165", "v166", "v167", "scc", "memory"
 __device__ __forceinline__ void nmc_rows_lds_linreg2_quad(const double* p, int nb,
                                                           const double (&c)[4],
                                                           const double (&dd)[4],
@@ -234,39 +266,53 @@ __device__ __forceinline__ void nmc_rows_lds_linreg2_quad(const double* p, int n
   unsigned addr = (unsigned)(uintptr_t)(nmc_lds_cptr)p;
   int cnt = nb;
   asm volatile(
-      NMC_Q4(120, 0)
-      "L_nmc_q_%=:\n"
-      "s_sub_u32 %[cnt], %[cnt], 1\n"
-      "s_cmp_gt_i32 %[cnt], 0\n"
-      "s_cbranch_scc0 L_nmc_qla_%=\n"
-      NMC_Q4(136, 256)
-      "s_waitcnt lgkmcnt(4)\n"
-      NMC_QBA
-      "v_add_u32 %[addr], 0x200, %[addr]\n"
-      "s_sub_u32 %[cnt], %[cnt], 1\n"
-      "s_cmp_gt_i32 %[cnt], 0\n"
-      "s_cbranch_scc0 L_nmc_qlb_%=\n"
-      NMC_Q4(120, 0)
-      "s_waitcnt lgkmcnt(4)\n"
-      NMC_QBB
-      "s_branch L_nmc_q_%=\n"
-      "L_nmc_qla_%=:\n"
-      "s_waitcnt lgkmcnt(0)\n"
-      NMC_QBA
-      "s_branch L_nmc_qend_%=\n"
-      "L_nmc_qlb_%=:\n"
-      "s_waitcnt lgkmcnt(0)\n"
-      NMC_QBB
-      "L_nmc_qend_%=:\n"
+      NMC_QLOOP
       : [addr] "+v"(addr), [cnt] "+s"(cnt), [a0] "+v"(a[0]), [a1] "+v"(a[1]), [a2] "+v"(a[2]),
         [a3] "+v"(a[3])
       : [c0] "v"(c[0]), [c1] "v"(c[1]), [c2] "v"(c[2]), [c3] "v"(c[3]), [d0] "v"(dd[0]),
         [d1] "v"(dd[1]), [d2] "v"(dd[2]), [d3] "v"(dd[3])
-      : "v120", "v121", "v122", "v123", "v124", "v125", "v126", "v127", "v128", "v129", "v130",
-        "v131", "v132", "v133", "v134", "v135", "v136", "v137", "v138", "v139", "v140", "v141",
-        "v142", "v143", "v144", "v145", "v146", "v147", "v148", "v149", "v150", "v151", "v152",
-        "v153", "v154", "v155", "v156", "v157", "v158", "v159", "v160", "v161", "v162", "v163",
-        "v164", "v165", "v166", "v167", "scc", "memory");
+      : NMC_QCLOBBERS);
+}
+// The same loop for a step's first tile in the step kernel's restart without gathers (step.h):
+// the four chains' intercepts and slopes are read here, from the parameters' LDS columns -- cp /
+// dp point at this lane's quarter position (lane & 15) of the intercept / slope column, whose
+// elements + 16j are chain slot j's -- and returned in c / dd for the step's later tiles.  The
+// eight reads go out back to back with the first block's row reads -- the rows do not depend on
+// the parameters -- and the loop's first wait covers both: one LDS round trip, where parameters
+// handed in as operands are waited for before the block.  ic == 0 (wave-uniform): the model has
+// no intercept, c = 0.0.
+__device__ __forceinline__ void nmc_rows_lds_linreg2_quad_first(const double* p, int nb, int ic,
+                                                                const double* cp,
+                                                                const double* dp, double (&c)[4],
+                                                                double (&dd)[4], double (&a)[4]) {
+  unsigned addr = (unsigned)(uintptr_t)(nmc_lds_cptr)p;
+  const unsigned ca = (unsigned)(uintptr_t)(nmc_lds_cptr)cp;
+  const unsigned da = (unsigned)(uintptr_t)(nmc_lds_cptr)dp;
+  int cnt = nb;
+  asm volatile(
+      "v_cmp_eq_u32_e32 vcc, 0, %[ic]\n"
+      "s_cbranch_vccnz L_nmc_qnc_%=\n"
+      "ds_read_b64 %[c0], %[ca]\n"
+      "ds_read_b64 %[c1], %[ca] offset:128\n"
+      "ds_read_b64 %[c2], %[ca] offset:256\n"
+      "ds_read_b64 %[c3], %[ca] offset:384\n"
+      "s_branch L_nmc_qd_%=\n"
+      "L_nmc_qnc_%=:\n"
+      "v_mov_b64 %[c0], 0\n"
+      "v_mov_b64 %[c1], 0\n"
+      "v_mov_b64 %[c2], 0\n"
+      "v_mov_b64 %[c3], 0\n"
+      "L_nmc_qd_%=:\n"
+      "ds_read_b64 %[d0], %[da]\n"
+      "ds_read_b64 %[d1], %[da] offset:128\n"
+      "ds_read_b64 %[d2], %[da] offset:256\n"
+      "ds_read_b64 %[d3], %[da] offset:384\n"
+      NMC_QLOOP
+      : [addr] "+v"(addr), [cnt] "+s"(cnt), [a0] "+v"(a[0]), [a1] "+v"(a[1]), [a2] "+v"(a[2]),
+        [a3] "+v"(a[3]), [c0] "=&v"(c[0]), [c1] "=&v"(c[1]), [c2] "=&v"(c[2]), [c3] "=&v"(c[3]),
+        [d0] "=&v"(dd[0]), [d1] "=&v"(dd[1]), [d2] "=&v"(dd[2]), [d3] "=&v"(dd[3])
+      : [ca] "v"(ca), [da] "v"(da), [ic] "v"(ic)
+      : "vcc", NMC_QCLOBBERS);
 }
 
 // v of the four lanes (lane & 15) + 16j, j = 0..3 (the lane's position in each quarter):
@@ -451,17 +497,34 @@ __device__ __forceinline__ void nmc_ll_rows_lds(const Fam& fam, const typename F
 // (nmc_quarters).  The 16-row blocks cover the broadcast loop's even number of 8-row blocks;
 // after the transpose the lane's own chain's four accumulators take the remaining rows in
 // order into a[0], as in nmc_ll_rows_lds -- every sum bit-identical to it.
-template <class Fam>
-__device__ __forceinline__ void nmc_ll_rows_lds_quad(const Fam& fam, const typename Fam::Reg& reg,
+// FIRST (step.h, the restart without gathers): the step's first tile, whose row loop reads c /
+// dd from the LDS columns at cp / dp (nmc_rows_lds_linreg2_quad_first) and returns them for the
+// later tiles; a first tile of fewer than 16 rows is the group's last tile and needs none.  The
+// lane's own chain (reg, for the rows beyond the 16-row blocks) is prepared here from thp, read
+// by the caller and first used behind the row loop: no LDS round trip of its own either.
+template <class Fam, bool FIRST = false, class RG, class QV>
+__device__ __forceinline__ void nmc_ll_rows_lds_quad(const Fam& fam, RG& reg,
                                                      const double* __restrict__ p, int n,
-                                                     double (&acc)[Fam::NACC],
-                                                     const double (&c)[4], const double (&dd)[4]) {
+                                                     double (&acc)[Fam::NACC], QV (&c)[4],
+                                                     QV (&dd)[4], const double* thp = nullptr,
+                                                     int ic = 0, const double* cp = nullptr,
+                                                     const double* dp = nullptr) {
   static_assert(Fam::ASM_ROWS && Fam::NFIELDS == 2 && Fam::NACC == 1, "{x, y} rows only");
   constexpr int NF = Fam::NFIELDS;
   const int q = (threadIdx.x >> 4) & 3;
   const int nb16 = (n / 8) >> 1;      // = the broadcast loop's (n / 8) & ~1 8-row blocks / 2
   double a[4] = {0.0, 0.0, 0.0, 0.0};
-  if (nb16 > 0) {
+  if constexpr (FIRST) {
+    if (nb16 > 0) {
+      __builtin_amdgcn_sched_barrier(0);   // (thp's reads are in flight, not waited for)
+      nmc_rows_lds_linreg2_quad_first(p + (size_t)q * NF, nb16, ic, cp, dp, c, dd, a);
+      nmc_transpose4(a);
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) c[j] = dd[j] = 0.0;
+    }
+    reg = fam.prepare(thp);
+  } else if (nb16 > 0) {
     nmc_rows_lds_linreg2_quad(p + (size_t)q * NF, nb16, c, dd, a);
     nmc_transpose4(a);
   }

@@ -114,6 +114,20 @@ nmc_k_run(Dev d_arg, Fam fam, const double* __restrict__ obs, int i0, int i1, in
   const bool quad = d.quad;
   const bool nstatic = d.nstatic;
   const bool ctlprio = !(d.noprio & 1);
+  // The restart without gathers (quad rows, P >= 2): step gs + 1 proposes another parameter
+  // than step gs decides, so the control wave forms its proposal a step ahead -- before
+  // barrier A of step gs -- and leaves it in the LDS column NMC_CW_PN; after barrier B the tile
+  // waves read the four chains of their quarter position straight from the parameters' columns
+  // (lik_tiles) instead of forming the proposal again, each, and gathering it across lanes.
+  // The first step of a call has no step before it and keeps the gathers.
+  constexpr bool QF = Fam::ASM_ROWS && RL && !HALF;
+  int qib0 = -1, qib = 0;   // the parameters that are the rows' intercept and slope
+  if constexpr (QF) {
+    fam.quad_params(qib0, qib);
+    qib0 = __builtin_amdgcn_readfirstlane(qib0);   // (scalar: the row loop branches on it)
+    qib = __builtin_amdgcn_readfirstlane(qib);
+  }
+  const bool fastq = QF && quad && d.P >= 2 && !(NMC_ZIN_BUILD && d.zin);
   const int mb = b % S;                           // row-split member (S == 1: 0)
   // (chain block, group) of unit u = b / S: chain-block-major, or (Dev.xpc > 0, S == 1) dealt
   // so that a chain block's workgroups share xpc XCDs -- blocks b and b + 8 share an XCD
@@ -326,30 +340,43 @@ nmc_k_run(Dev d_arg, Fam fam, const double* __restrict__ obs, int i0, int i1, in
   //      after its first tile (the control wave's pre-barrier work) ----
   auto lik_tiles = [&](int t, int p, int sp, auto&& between) {
     if (w == 2) NMC_CS((t - i0) * P + p, 12);
-    // every LDS read of the restart issued before any is used: one round trip (left alone
-    // the scheduler waits for the values before it issues the scale and variate reads)
-    const double sv = st[(NMC_ST_S * P + p) * 64], zv = lds[(L.zl + 2 * sp) * 64 + 2 * lane];
-    double thp[Fam::MAXP];
-#pragma unroll
-    for (int q = 0; q < Fam::MAXP; ++q) thp[q] = q < P ? th[q * 64] : 0.0;
-    __builtin_amdgcn_sched_barrier(0);
-    double vp = 0.0;   // thp[p] (a select per parameter: no dynamically indexed array)
-#pragma unroll
-    for (int q = 0; q < Fam::MAXP; ++q)
-      if (q == p) vp = thp[q];
-    const double prop = vp + (1.0 * sv) * zv;
-#pragma unroll
-    for (int q = 0; q < Fam::MAXP; ++q)
-      if (q == p) thp[q] = prop;
-    const typename Fam::Reg reg = fh.prepare(thp);
+    // the proposal was formed a step ahead (fastq above; not at the first step of a call)
+    const bool ahead = fastq && t * P + p > gfirst;
+    typename Fam::Reg reg;
     // quad rows: intercept and slope of the four chains of this lane's quarter position
+    // (ahead: the first tile's row loop reads them, below)
     double qc[4], qd[4];
-    if constexpr (Fam::ASM_ROWS && RL && !HALF) if (quad) {
-      nmc_quarters(reg.b0, qc);
-      nmc_quarters(reg.b[0], qd);
+    double thp[Fam::MAXP];
+    if (ahead) {
+      // this lane's own chain, for the tiles' rows beyond the 16-row blocks: read only, prepared
+      // behind the first tile's row loop
+#pragma unroll
+      for (int q = 0; q < Fam::MAXP; ++q)
+        thp[q] = q < P ? (q == p ? cwv[NMC_CW_PN * 64] : th[q * 64]) : 0.0;
+    } else {
+      // every LDS read of the restart issued before any is used: one round trip (left alone
+      // the scheduler waits for the values before it issues the scale and variate reads)
+      const double sv = st[(NMC_ST_S * P + p) * 64], zv = lds[(L.zl + 2 * sp) * 64 + 2 * lane];
+#pragma unroll
+      for (int q = 0; q < Fam::MAXP; ++q) thp[q] = q < P ? th[q * 64] : 0.0;
+      __builtin_amdgcn_sched_barrier(0);
+      double vp = 0.0;   // thp[p] (a select per parameter: no dynamically indexed array)
+#pragma unroll
+      for (int q = 0; q < Fam::MAXP; ++q)
+        if (q == p) vp = thp[q];
+      const double prop = vp + (1.0 * sv) * zv;
+#pragma unroll
+      for (int q = 0; q < Fam::MAXP; ++q)
+        if (q == p) thp[q] = prop;
+      reg = fh.prepare(thp);
+      if constexpr (QF) if (quad) {
+        nmc_quarters(reg.b0, qc);
+        nmc_quarters(reg.b[0], qd);
+      }
     }
     // paired rows: the partner lane's (lane ^ 32) proposal parameters
-    typename Fam::Reg preg = reg;
+    typename Fam::Reg preg{};   // (ahead: quad rows, no partner)
+    if (!ahead) preg = reg;
     if constexpr (nmc_paired_rows_ok<Fam>() && !HALF) if (paired && !quad) {
       const bool hi = lane >= 32;
 #pragma unroll
@@ -361,22 +388,55 @@ nmc_k_run(Dev d_arg, Fam fam, const double* __restrict__ obs, int i0, int i1, in
     }
     if (w == 2) NMC_CS((t - i0) * P + p, 13);
     // the next tile is requested before the current one is computed: the atomic's
-    // return rides under the tile's own row reads
+    // return rides under the tile's own row reads.  Families with the hand-written row loops:
+    // nmc_lds_grab, not behind this wave's outstanding global memory (its value only through
+    // nmc_lds_grab_value).  The compiled row loops keep the compiler's atomic, whose return it
+    // tracks through their reads: with nmc_lds_grab cfg 2 measured 2.7 % slower.
     auto grab = [&]() -> unsigned {
-      unsigned k = 0;
-      if (lane == 0)
-        k = __hip_atomic_fetch_add(tcnt + sp, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      return k;
+      if constexpr (Fam::ASM_ROWS) {
+        return nmc_lds_grab(tcnt + sp);
+      } else {
+        unsigned k = 0;
+        if (lane == 0)
+          k = __hip_atomic_fetch_add(tcnt + sp, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        return k;
+      }
+    };
+    auto grabbed = [&](unsigned r) -> int {
+      if constexpr (Fam::ASM_ROWS) return nmc_lds_grab_value(r);
+      else return (int)__builtin_amdgcn_readlane(r, 0);
     };
     // d.zin: queue entry 0 is the next step's variate job, entries 1.. the tiles
     const int tn = p + 1 < P ? t : t + 1, pn = p + 1 < P ? p + 1 : 0;
     const int zj = NMC_ZIN_BUILD && d.zin && tn < ie ? 1 : 0;
     // (waves 2.. start on their static entry: one LDS round trip off the step's restart)
     int kq = nstatic && w >= 2 ? (w - 2 < nt + zj ? w - 2 : nt + zj)
-                               : (int)__builtin_amdgcn_readlane(grab(), 0);
+                               : grabbed(grab());
 #ifdef NMC_CSTAMPS
     bool first_tile = true;
 #endif
+    // ahead: the wave's first tile apart -- its row loop reads qc / qd, this lane's quarter
+    // position (lane & 15) of the intercept's and the slope's columns (NMC_CW_PN for the
+    // proposed parameter), beside its first rows, for the step's later tiles too (zj == 0)
+    if constexpr (QF) if (ahead && kq < nt) {
+      const unsigned kn = grab();
+#ifdef NMC_CSTAMPS
+      NMC_CS((t - i0) * P + p, 16 + w);
+      first_tile = false;
+#endif
+      const double* col = lds + (lane & 15);
+      const int cc0 = qib0 == p ? L.cw + NMC_CW_PN : L.th + (qib0 < 0 ? 0 : qib0);
+      const int cc1 = qib == p ? L.cw + NMC_CW_PN : L.th + qib;
+      NMC_TILE_STAMP(kq, 0);
+      double acc[Fam::NACC];
+      nmc_ll_rows_lds_quad<Fam, true>(fh, reg, lrows + (size_t)TI.start(kq) * Fam::NFIELDS,
+                                      TI.len(kq), acc, qc, qd, thp, qib0 >= 0,
+                                      col + cc0 * 64, col + cc1 * 64);
+      lds[(L.part + kq) * 64 + lane] = acc[0];
+      NMC_TILE_STAMP(kq, 1);
+      between();
+      kq = grabbed(kn);
+    }
     while (kq < nt + zj) {
       const unsigned kn = grab();
 #ifdef NMC_CSTAMPS
@@ -385,7 +445,7 @@ nmc_k_run(Dev d_arg, Fam fam, const double* __restrict__ obs, int i0, int i1, in
 #endif
       if (kq < zj) {   // the variate job: {z, log u} of the next step -> the other slot
         gen_zl(tn, pn, sp ^ 1);
-        kq = (int)__builtin_amdgcn_readlane(kn, 0);
+        kq = grabbed(kn);
         continue;
       }
       const int k = kq - zj;
@@ -420,7 +480,7 @@ nmc_k_run(Dev d_arg, Fam fam, const double* __restrict__ obs, int i0, int i1, in
       for (int j = 0; j < Fam::NACC; ++j) lds[(L.part + j * NMC_NSLOT + k) * 64 + lane] = acc[j];
       NMC_TILE_STAMP(k, 1);
       between();
-      kq = (int)__builtin_amdgcn_readlane(kn, 0);
+      kq = grabbed(kn);
     }
   };
   // ---- register mode: the Gibbs wave runs its own loop (gibbs_step below), so its 64-value
@@ -799,7 +859,10 @@ nmc_k_run(Dev d_arg, Fam fam, const double* __restrict__ obs, int i0, int i1, in
         if (pend_p >= 0) apply_pending();
         c_v = th[p * 64];
         const double s = st[(NMC_ST_S * P + p) * 64];
-        c_prop = c_v + (1.0 * s) * lds[(L.zl + 2 * sp) * 64 + 2 * lane];   // propose (:304-306)
+        if (fastq && gs > gfirst)   // formed a step ahead (below, before barrier A)
+          c_prop = cwv[NMC_CW_PN * 64];
+        else
+          c_prop = c_v + (1.0 * s) * lds[(L.zl + 2 * sp) * 64 + 2 * lane];   // propose (:304-306)
         c_lu = lds[(L.zl + 2 * sp) * 64 + 2 * lane + 1];
         {
           double thp[Fam::MAXP];
@@ -874,8 +937,20 @@ nmc_k_run(Dev d_arg, Fam fam, const double* __restrict__ obs, int i0, int i1, in
       if (ctl && ctlprio) __builtin_amdgcn_s_setprio(3);
       NMC_STAMP(t, 1 + 3 * (p & 1));
       if (ctl || (hl && !pipe && gw)) nmc_drain_vm();   // this wave's LDS-DMA has landed
+      // the next step's proposal (fastq), the expression of ctl_work: that step proposes
+      // another parameter (P >= 2), whose value and scale no decision in between changes, and
+      // its variates have just landed.  Written after barrier A, when every wave has read this
+      // step's from the column, and read after barrier B.
+      const bool pn_now = ctl && fastq && (p + 1 < P ? t : t + 1) < ie;
+      double c_pn = 0.0;
+      if (pn_now) {
+        const int pn = p + 1 < P ? p + 1 : 0;
+        c_pn = th[pn * 64] + (1.0 * st[(NMC_ST_S * P + pn) * 64]) *
+                                 lds[(L.zl + 2 * (sp ^ 1)) * 64 + 2 * lane];
+      }
       NMC_CS(gs - gs0, w);
       nmc_step_barrier();   // A
+      if (pn_now) cwv[NMC_CW_PN * 64] = c_pn;
       NMC_STAMP(t, 2 + 3 * (p & 1));
       if (ctl) NMC_CS(gs - gs0, 8);
 
