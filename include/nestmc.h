@@ -182,6 +182,20 @@ int nmc_obs_ll_rows(nmc_ctx* ctx, int row_begin, int n_rows, double* out);
  * the host formats the previous batch with `threads` threads; a chain whose id is
  * negative gets no file (a rank's padding chains).                             */
 int nmc_write_ll_csvs(nmc_ctx* ctx, const char* dir, const int32_t* chain_ids, int threads);
+/* WAIC's reduction of that per-observation LL (StepMethod.logLikelihood :656-659 at the
+ * recorded values of :890-891, the rows saveLogLikelihood prints at :907-909) over recorded
+ * rows [row_begin, row_begin+n_rows) and local chains [0, n_valid), on the device and without
+ * forming the matrix; the reduction itself has no counterpart in the reference, whose users
+ * compute it from the files.  part[CB][5][n_obs], CB = ceil(C / 64): per chain block and
+ * observation the combinable state (m, s, n, mean, M2) -- m = max ll, s = sum exp(ll - m),
+ * n = samples, Welford's mean and M2 -- with the block's 64 chains merged in a fixed order
+ * (csrc/waic.h; nestmc/waic.py merges the blocks and finishes).  Chains >= n_valid (a rank's
+ * padding) enter as the identity (-inf, 0, 0, 0, 0).  1 <= n_valid <= C, n_rows >= 1 and the
+ * rows inside the schedule's, else -1; any number of rows per call.  *nonfinite: the terms
+ * that were not finite (they propagate into the state; callers treat a count as an error).
+ * Event slots 14 and 15 bracket the kernel.                                      */
+int nmc_waic_partials(nmc_ctx* ctx, int row_begin, int n_rows, int n_valid, double* part,
+                      int64_t* nonfinite);
 
 /* Timing on the context's stream (hipEvents). */
 int nmc_event_record(nmc_ctx* ctx, int slot);                 /* slot 0..15 */

@@ -92,6 +92,9 @@ struct nmc_ctx {
   int ncu = 256;
   int* gidx = nullptr;                    // [n_obs] group of each observation (obs-LL rows)
   int64_t nmax_group = 0;                 // rows of the largest group
+  nmc_waic_tile* wtiles = nullptr;        // [n_wtiles] observation tiles of nmc_k_waic (waic.h)
+  int n_wtiles = 0;
+  unsigned long long* wbad = nullptr;     // non-finite terms nmc_k_waic met (zeroed per call)
   int split_batch = 0;                    // row split: chain blocks per (resident) launch
   int sweep_batch = 0;                    // nmc_k_sweep with Dev.gsep: chain blocks per launch
   unsigned gepoch = 0;                    // Dev.gsep launches so far (Dev.gep)
@@ -268,13 +271,15 @@ enum {
   NMC_OP_OBS_LL = 3,       // in = values [P][G][C] (device), out = [C][n_obs] (device)
   NMC_OP_OBS_LL_ROWS = 4,  // sample rows [i0, i1), chains [c0, c0 + nc) -> out = [nc][i1 - i0][n_obs]
   NMC_OP_CAPACITY = 5,     // result = resident step-kernel workgroups on the device
-  NMC_OP_RES_OK = 6        // result = 1: the run mode has a resident instance, grid co-resident
+  NMC_OP_RES_OK = 6,       // result = 1: the run mode has a resident instance, grid co-resident
+  NMC_OP_WAIC = 7          // sample rows [i0, i1), chains < nc valid -> out = [CB][5][n_obs] (waic.h)
 };
 struct NmcCall {
   int op = 0;
   int i0 = 0, i1 = 0, flags = 0;
   int res = 0;             // NMC_OP_RUN: the resident instance (Dev.rcmd set)
   int c0 = 0, nc = 0;      // NMC_OP_OBS_LL_ROWS: chains [c0, c0 + nc) (nc = 0: every chain)
+                           // NMC_OP_WAIC: nc = the valid chains (the others are padding)
   const double* in = nullptr;
   double* out = nullptr;
   double* aux = nullptr;   // op-specific device scratch

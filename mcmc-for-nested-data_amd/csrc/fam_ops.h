@@ -113,6 +113,16 @@ static int nmc_fam_call(nmc_ctx* x, const Fam& fam, NmcCall& c) {
       HIPCHK(hipGetLastError());
       return 0;
     }
+    case NMC_OP_WAIC: {
+      if (x->n_wtiles == 0) return 0;
+      const dim3 grid((unsigned)((x->n_wtiles + 3) / 4), (unsigned)x->d.CB);
+      hipLaunchKernelGGL(nmc_k_waic<Fam>, grid, dim3(256), 0, x->stream, x->d, fam, x->d.obs,
+                         (const nmc_waic_tile*)x->wtiles, x->n_wtiles, x->n_obs,
+                         x->pooling == NMC_POOL_PARTIAL ? 2 : 0, c.i0, c.i1 - c.i0, c.nc, c.out,
+                         x->wbad);
+      HIPCHK(hipGetLastError());
+      return 0;
+    }
     case NMC_OP_OBS_LL:
       hipLaunchKernelGGL(nmc_k_obs_ll<Fam>, dim3(x->d.CB * x->G), dim3(64), 0, x->stream, x->d,
                          fam, c.in, c.out, x->n_obs);

@@ -44,3 +44,4 @@
 #include "gibbs.h"       // hyper-parameter Gibbs update, row-split exchange
 #include "step.h"        // nmc_k_run, tuning, the step variates
 #include "ll_kernels.h"  // group and per-observation log-likelihood kernels
+#include "waic.h"        // WAIC: per-observation reduction over the sample store

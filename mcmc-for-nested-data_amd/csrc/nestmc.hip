@@ -1564,6 +1564,65 @@ int nmc_obs_ll_rows(nmc_ctx* x, int row_begin, int n_rows, double* out) {
   return rc;
 }
 
+// observation tiles of nmc_k_waic (waic.h): every group cut into runs of <= NMC_WAIC_T
+// consecutive observations, built once per context with the kernel's counter
+static int ensure_waic_tiles(nmc_ctx* x) {
+  if (x->wbad) return 0;
+  std::vector<int64_t> off(x->G + 1);
+  HIPCHK(hipMemcpy(off.data(), x->d.off, (x->G + 1) * sizeof(int64_t), hipMemcpyDeviceToHost));
+  std::vector<nmc_waic_tile> t;
+  for (int g = 0; g < x->G; ++g)
+    for (int64_t i = off[g]; i < off[g + 1]; i += NMC_WAIC_T)
+      t.push_back({i, g, (int)std::min<int64_t>(NMC_WAIC_T, off[g + 1] - i)});
+  if (t.size() > (size_t)0x7fffffff - 4) return fail(-1, "too many observations for WAIC tiles");
+  if (int rc = dalloc(x, &x->wtiles, t.size())) return rc;
+  if (!t.empty())
+    HIPCHK(hipMemcpy(x->wtiles, t.data(), t.size() * sizeof(nmc_waic_tile),
+                     hipMemcpyHostToDevice));
+  x->n_wtiles = (int)t.size();
+  return dalloc(x, &x->wbad, 1);
+}
+
+// WAIC's per-observation reduction of the LL of :656-659 at the recorded rows (:890-891,
+// :907-909) -- the reduction itself has no reference counterpart (include/nestmc.h).  The row
+// loop runs inside the kernel: no limit on the rows of a call.
+int nmc_waic_partials(nmc_ctx* x, int row_begin, int n_rows, int n_valid, double* part,
+                      int64_t* nonfinite) {
+  RES_PARK(x);
+  hipSetDevice(x->device);
+  if (row_begin < 0 || n_rows < 1 || row_begin > x->d.n_rows - n_rows)
+    return fail(-1, "row range out of bounds (at least one recorded row)");
+  if (n_valid < 1 || n_valid > x->C) return fail(-1, "n_valid must be in 1..n_chains");
+  HIPCHK(hipStreamSynchronize(x->stream));
+  if (int rc = check_timeout(x)) return rc;
+  if (int rc = ensure_waic_tiles(x)) return rc;
+  *nonfinite = 0;
+  const size_t n = (size_t)x->d.CB * 5 * x->n_obs;
+  if (n == 0) return 0;
+  double* o = nullptr;
+  HIPCHK(hipMalloc(&o, n * 8));
+  hipError_t e = hipMemsetAsync(x->wbad, 0, 8, x->stream);
+  NmcCall c;
+  c.op = NMC_OP_WAIC;
+  c.i0 = row_begin;
+  c.i1 = row_begin + n_rows;
+  c.nc = n_valid;
+  c.out = o;
+  int rc = e == hipSuccess ? nmc_event_record(x, 14) : 0;
+  if (!rc && e == hipSuccess) rc = nmc_call_family(x, c);
+  if (!rc && e == hipSuccess) rc = nmc_event_record(x, 15);
+  if (!rc) {
+    unsigned long long bad = 0;
+    if (e == hipSuccess) e = hipMemcpyAsync(part, o, n * 8, hipMemcpyDeviceToHost, x->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(&bad, x->wbad, 8, hipMemcpyDeviceToHost, x->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(x->stream);
+    if (e != hipSuccess) rc = fail(-2, std::string("waic_partials: ") + hipGetErrorString(e));
+    *nonfinite = (int64_t)bad;
+  }
+  hipFree(o);
+  return rc;
+}
+
 // saveLogLikelihood (Sampler._printLogLikelihood :907-909 at every recorded row, the LL
 // of :656-659 evaluated at the recorded values): batches are evaluated on the device into
 // one of two buffers and copied to pinned host memory while the host formats and appends

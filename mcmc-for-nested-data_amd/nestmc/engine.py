@@ -207,6 +207,33 @@ class Engine:
                                          ids.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
                                          int(threads)))
 
+    def waic_partials(self, row_begin=0, n_rows=None, n_valid=None):
+        """WAIC's per-observation state (m, s, n, mean, M2) of every chain block over recorded
+        rows [row_begin, row_begin + n_rows) and local chains [0, n_valid): [CB, 5, n_obs],
+        reduced on the device from the sample store (nmc_waic_partials; nestmc.waic).  Chains
+        from n_valid on (padding) enter as the identity.  A term that is not finite is an
+        error."""
+        if n_rows is None:
+            n_rows = self.n_rows - row_begin
+        if n_valid is None:
+            n_valid = self.C
+        out = numpy.empty(((self.C + 63) // 64, 5, int(self.off[-1])))
+        bad = ctypes.c_int64()
+        check(self.lib.nmc_waic_partials(self.h, int(row_begin), int(n_rows), int(n_valid),
+                                         dptr(out), ctypes.byref(bad)))
+        self.waic_nonfinite = bad.value
+        if bad.value:
+            raise _lib.NestmcError("WAIC: %d per-observation log-likelihood terms were not "
+                                   "finite" % bad.value)
+        return out
+
+    def waic(self, row_begin=0, n_rows=None, n_valid=None):
+        """The WaicResult (nestmc.waic) of this engine's chains: its chain blocks' partials
+        merged in chain-block order."""
+        from . import waic as _waic
+        parts = self.waic_partials(row_begin, n_rows, n_valid)
+        return _waic.finish(_waic.merge(list(parts)), self.off)
+
     def eval_obs_ll(self):
         """Per-observation LL at the current state: [C, n_obs]."""
         out = numpy.empty((self.C, int(self.off[-1])))

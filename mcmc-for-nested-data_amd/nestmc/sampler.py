@@ -23,6 +23,7 @@ import numpy
 
 from . import _lib
 from . import output
+from . import waic as _waic
 from .engine import Engine
 from .families import is_family
 from .init import init_chains
@@ -60,7 +61,8 @@ def sample_posterior(nChains, nIter, nSamples, parameterName, nGroups, nResponse
                      priorDistribution=None, startWithMLE=False, startingPointValueRange=None,
                      nProcesses=1, displayProgress=True, loggingLevel="info", *,
                      seed=0, devices=None, rng="philox", chains=None, return_samples=False,
-                     write_files=True, replay=None, process_per_device=False, _rank=None):
+                     write_files=True, replay=None, process_per_device=False, _rank=None,
+                     computeWaic=False):
     """Drop-in for posteriorSampling.samplePosterior (same positional/keyword API).
 
     Extra keyword-only options (all optional):
@@ -79,6 +81,11 @@ def sample_posterior(nChains, nIter, nSamples, parameterName, nGroups, nResponse
                  hz, hu [C, iter, P] (chain axis = position in ``chains``)
       chains     run only these global chain ids (multi-process sharding)
       return_samples  also return {"rows": [C][rows][cols], "row_index", "header"}
+      computeWaic  after the loop, reduce the per-observation log-likelihood of every
+                 recorded row (the numbers saveLogLikelihood would print) to WAIC on the
+                 GPU (nestmc.waic): outputDirectory/waic.csv and waic_pointwise.csv, and
+                 "waic" (a nestmc.waic.WaicResult) in the returned dict; needs no
+                 logLikelihood files, so saveLogLikelihood may be False
     nProcesses sizes the host threads used for chain initialisation and CSV writing.
     """
     start_time = datetime.datetime.now()
@@ -158,7 +165,8 @@ def sample_posterior(nChains, nIter, nSamples, parameterName, nGroups, nResponse
                   startWithMLE=startWithMLE, startingPointValueRange=startingPointValueRange,
                   nProcesses=max(1, threads // len(devices)), displayProgress=displayProgress,
                   loggingLevel=loggingLevel, seed=seed, rng=rng,
-                  return_samples=return_samples, write_files=write_files)
+                  return_samples=return_samples, write_files=write_files,
+                  computeWaic=computeWaic)
         res = ranks.run_per_device(kw, devices)
         _finish_log(logger, [], start_time, displayProgress)
         return res
@@ -235,7 +243,9 @@ def sample_posterior(nChains, nIter, nSamples, parameterName, nGroups, nResponse
     try:
         return _sample_loop(engines, nIter, burn, thin, names, G, partial, saveLogLikelihood,
                             write_files, sample_dir, threads, displayProgress, return_samples,
-                            logger, chain_logs, start_time, rank_info)
+                            logger, chain_logs, start_time, rank_info,
+                            compute_waic=bool(computeWaic), waic_dir=outputDirectory,
+                            n_real=nChains)
     finally:
         for eng, _, _ in engines:
             eng.close()
@@ -279,9 +289,33 @@ def _gather_rank(engines, rank_info):
     return raw, numpy.concatenate(accs, axis=0)
 
 
+def _waic_of(engines, rank_info, n_real):
+    """computeWaic: every engine's chain-block partials over all recorded rows (its padding
+    chains, ids >= n_real, as the identity), merged in engine order; the ranks of
+    process_per_device send theirs over the host group and rank 0 merges them in rank order
+    (the other ranks: None)."""
+    parts = []
+    for eng, _, ids in engines:
+        n_valid = sum(1 for c in ids if c < n_real)
+        if n_valid > 0:
+            parts.extend(eng.waic_partials(n_valid=n_valid))
+        else:
+            parts.append(_waic.identity(int(eng.off[-1])))
+    part = _waic.merge(parts)
+    off = engines[0][0].off
+    if rank_info is not None:
+        got = rank_info["hg"].gather(numpy.ascontiguousarray(part).tobytes())
+        if rank_info["rank"] != 0:
+            return None
+        part = _waic.merge_ranks([numpy.frombuffer(b, dtype=numpy.float64).reshape(5, -1)
+                                  for b in got])
+    return _waic.finish(part, off)
+
+
 def _sample_loop(engines, nIter, burn, thin, names, G, partial, saveLogLikelihood, write_files,
                  sample_dir, threads, displayProgress, return_samples, logger, chain_logs,
-                 start_time, rank_info=None):
+                 start_time, rank_info=None, compute_waic=False, waic_dir=None,
+                 n_real=None):
     """The device loop, the per-observation LL rows and the sample files of
     sample_posterior (the caller closes the engines whatever happens here).  rank_info: a
     rank of process_per_device -- this rank writes its chains' logLikelihood files, rank 0
@@ -318,6 +352,12 @@ def _sample_loop(engines, nIter, burn, thin, names, G, partial, saveLogLikelihoo
             fids = ids if n_total is None else [c if c < n_total else -1 for c in ids]
             eng.write_ll_csvs(sample_dir, fids, threads=threads)
 
+    waic_result = None
+    if compute_waic:
+        waic_result = _waic_of(engines, rank_info, n_real)
+        if waic_result is not None and write_files:
+            _waic.write_csvs(waic_result, waic_dir)
+
     # ---- samples -> files ----------------------------------------------------
     header = output.header_names(names, G, partial)
     hdr = header if burn < nIter else None
@@ -345,8 +385,11 @@ def _sample_loop(engines, nIter, burn, thin, names, G, partial, saveLogLikelihoo
     if rank_info is not None and rank_info["rank"] != 0:
         return None
     if return_samples:
-        return {"rows": numpy.concatenate(rows_all, axis=0), "row_index": rec,
-                "header": header, "burn": burn, "thin": thin,
-                "accepted": numpy.concatenate(accept, axis=0),
-                "loop_seconds": loop_seconds}
+        res = {"rows": numpy.concatenate(rows_all, axis=0), "row_index": rec,
+               "header": header, "burn": burn, "thin": thin,
+               "accepted": numpy.concatenate(accept, axis=0),
+               "loop_seconds": loop_seconds}
+        if waic_result is not None:
+            res["waic"] = waic_result
+        return res
     return None

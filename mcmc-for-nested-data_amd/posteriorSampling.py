@@ -23,12 +23,15 @@ def samplePosterior(nChains, nIter, nSamples,
                     saveLogLikelihood=True,
                     priorDistribution=None,
                     startWithMLE=False, startingPointValueRange=None,
-                    nProcesses=1, displayProgress=True, loggingLevel="info", **gpu_options):
+                    nProcesses=1, displayProgress=True, loggingLevel="info",
+                    computeWaic=False, **gpu_options):
     """Sample the posterior of a nested model; samples go to outputDirectory/sample/.
 
     Arguments mirror the reference (posteriorSampling.py:28-145).  Keyword-only
     GPU options: seed, devices, rng, chains, return_samples (nestmc.sampler).
-    Returns None like the reference unless return_samples=True.
+    computeWaic=True also reduces the per-observation log-likelihood of the recorded rows
+    to WAIC on the GPU (waic.csv, waic_pointwise.csv; nestmc.waic), with or without
+    saveLogLikelihood.  Returns None like the reference unless return_samples=True.
     """
     return sample_posterior(nChains, nIter, nSamples, parameterName, nGroups,
                             nResponsesPerGroup, pooling, logLikelihoodFunction,
@@ -36,4 +39,5 @@ def samplePosterior(nChains, nIter, nSamples,
                             priorDistribution=priorDistribution, startWithMLE=startWithMLE,
                             startingPointValueRange=startingPointValueRange,
                             nProcesses=nProcesses, displayProgress=displayProgress,
-                            loggingLevel=loggingLevel, **gpu_options)
+                            loggingLevel=loggingLevel, computeWaic=computeWaic,
+                            **gpu_options)
