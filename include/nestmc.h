@@ -100,8 +100,21 @@ int nmc_destroy(nmc_ctx* ctx);
 int nmc_set_state(nmc_ctx* ctx, const double* value, const double* log_prior,
                   const double* ll, const double* hyper_mu, const double* hyper_sigma2,
                   const double* scale);
+/* The chain state after the last iteration run (any pointer may be NULL).
+ * None / complete pooling: no hyper-parameters exist, hyper_mu and hyper_sigma2
+ * come back as NaN.  Partial pooling: log_prior is the device's own copy, each
+ * value's log prior under the hyper-parameters of the step that decided it (the
+ * step kernels recompute the current one and never read it back); the
+ * reference's quantity is nmc_get_log_prior's.                                 */
 int nmc_get_state(nmc_ctx* ctx, double* value, double* log_prior, double* ll,
                   double* hyper_mu, double* hyper_sigma2, double* scale);
+/* The log priors [P][G][C] as the reference holds them after the last iteration.
+ * Partial pooling, once an iteration has run: norm.logpdf(value, mu,
+ * sqrt(sigma2)) under the CURRENT hyper-parameters (setPrior :273-282 after
+ * every Gibbs update), evaluated on the host from the state nmc_get_state
+ * returns, y = (x - loc) / scale as nmc_norm_logpdf.  Before any iteration, and
+ * under none / complete pooling: nmc_get_state's log_prior.                   */
+int nmc_get_log_prior(nmc_ctx* ctx, double* log_prior);
 
 /* Replay variates [n_iter] (RNG mode NMC_RNG_REPLAY). */
 int nmc_set_replay(nmc_ctx* ctx, const double* z, const double* u,

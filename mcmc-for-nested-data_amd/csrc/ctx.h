@@ -87,6 +87,7 @@ struct nmc_ctx {
   int launch_iters = 0;                    // cap on iterations per launch (0: vcap)
   std::vector<int> kev_iters;             // iterations covered by each timed step launch
   int cur_slot = 1;                       // state after the last iteration: slot cur_slot
+  bool lp_as_set = true;                  // no iteration since nmc_set_state: d.lp is as given
   int nacc = 1;                           // likelihood accumulators of the family
   bool persistent = false;                // partial pooling: one resident launch per chunk
   int ncu = 256;

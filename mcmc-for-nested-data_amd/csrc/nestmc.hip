@@ -16,6 +16,8 @@
 #include <atomic>
 #include <charconv>
 #include <chrono>
+#include <cmath>
+#include <limits>
 #include <string>
 #include <thread>
 #include <utility>
@@ -838,6 +840,7 @@ int nmc_set_state(nmc_ctx* x, const double* value, const double* log_prior, cons
   const size_t PGC = (size_t)x->P * x->G * x->C, GC = (size_t)x->G * x->C, PC = (size_t)x->P * x->C;
   HIPCHK(hipMemcpy(d.vb1, value, PGC * 8, hipMemcpyHostToDevice));
   x->cur_slot = 1;
+  x->lp_as_set = true;
   HIPCHK(hipMemcpy(d.lp, log_prior, PGC * 8, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(d.ll, ll, GC * 8, hipMemcpyHostToDevice));
   if (x->pooling == NMC_POOL_PARTIAL) {
@@ -872,10 +875,55 @@ int nmc_get_state(nmc_ctx* x, double* value, double* log_prior, double* ll, doub
   if (value) HIPCHK(hipMemcpy(value, vslot(x, x->cur_slot), PGC * 8, hipMemcpyDeviceToHost));
   if (log_prior) HIPCHK(hipMemcpy(log_prior, d.lp, PGC * 8, hipMemcpyDeviceToHost));
   if (ll) HIPCHK(hipMemcpy(ll, d.ll, GC * 8, hipMemcpyDeviceToHost));
+  if (scale) HIPCHK(hipMemcpy(scale, d.scale, PGC * 8, hipMemcpyDeviceToHost));
+  if (x->pooling != NMC_POOL_PARTIAL) {
+    // no hyper-parameters exist (d.mu / d.s2 are never written): NaN, not device memory
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    for (size_t i = 0; i < PC; ++i) {
+      if (hyper_mu) hyper_mu[i] = nan;
+      if (hyper_sigma2) hyper_sigma2[i] = nan;
+    }
+    return 0;
+  }
   const size_t ho = (size_t)x->cur_slot * PC;
   if (hyper_mu) HIPCHK(hipMemcpy(hyper_mu, d.mu + ho, PC * 8, hipMemcpyDeviceToHost));
   if (hyper_sigma2) HIPCHK(hipMemcpy(hyper_sigma2, d.s2 + ho, PC * 8, hipMemcpyDeviceToHost));
-  if (scale) HIPCHK(hipMemcpy(scale, d.scale, PGC * 8, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int nmc_get_log_prior(nmc_ctx* x, double* log_prior) {
+  RES_PARK(x);
+  hipSetDevice(x->device);
+  HIPCHK(hipStreamSynchronize(x->stream));
+  Dev& d = x->d;
+  const size_t PGC = (size_t)x->P * x->G * x->C, PC = (size_t)x->P * x->C;
+  if (!log_prior) return fail(-1, "nmc_get_log_prior: null output");
+  // none / complete pooling: the accepted values' own log priors.  Partial pooling before any
+  // iteration: the start's (the reference leaves a redrawn start value's stale, :284-285)
+  if (x->pooling != NMC_POOL_PARTIAL || x->lp_as_set) {
+    HIPCHK(hipMemcpy(log_prior, d.lp, PGC * 8, hipMemcpyDeviceToHost));
+    return 0;
+  }
+  // The reference's quantity (setPrior :273-282 after every Gibbs update): each value's log
+  // prior under the CURRENT hyper-parameters, the division form of nmc_norm_logpdf.  d.lp
+  // holds it under the hyper-parameters in force when the value was decided (the step
+  // kernels recompute the current one for t > 0 and never read d.lp back).
+  const size_t ho = (size_t)x->cur_slot * PC;
+  std::vector<double> v(PGC), m(PC), s2(PC);
+  HIPCHK(hipMemcpy(v.data(), vslot(x, x->cur_slot), PGC * 8, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(m.data(), d.mu + ho, PC * 8, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(s2.data(), d.s2 + ho, PC * 8, hipMemcpyDeviceToHost));
+  const size_t C = x->C, G = x->G;
+  for (size_t p = 0; p < (size_t)x->P; ++p)
+    for (size_t c = 0; c < C; ++c) {
+      const double loc = m[p * C + c], sd = sqrt(s2[p * C + c]), lsd = log(sd);
+      for (size_t g = 0; g < G; ++g) {
+        const size_t i = (p * G + g) * C + c;
+        const double y = (v[i] - loc) / sd;
+        log_prior[i] = (!(sd > 0.0) || std::isnan(y)) ? std::numeric_limits<double>::quiet_NaN()
+                                                      : (-(y * y) / 2.0 - NMC_LOG_C) - lsd;
+      }
+    }
   return 0;
 }
 
@@ -987,6 +1035,7 @@ int nmc_run(nmc_ctx* x, int iter_begin, int iter_end) {
   if (iter_begin == iter_end) return 0;
   if (x->rng == NMC_RNG_REPLAY && (!x->d.rz || iter_end > x->d.replay_n))
     return fail(-1, "replay variates do not cover the iteration range");
+  x->lp_as_set = false;
   // a persistent launch that already timed out: stop before queueing more work
   if (int rc0 = check_timeout(x)) return rc0;
   tr.mark("tmo");

@@ -42,6 +42,7 @@ SIGNATURES = {
                                      _c_double_p, _c_double_p]),
     "nmc_get_state": (ctypes.c_int, [_vp, _c_double_p, _c_double_p, _c_double_p, _c_double_p,
                                      _c_double_p, _c_double_p]),
+    "nmc_get_log_prior": (ctypes.c_int, [_vp, _c_double_p]),
     "nmc_set_replay": (ctypes.c_int, [_vp, _c_double_p, _c_double_p, _c_double_p, _c_double_p,
                                       ctypes.c_int]),
     "nmc_set_schedule": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,

@@ -102,6 +102,15 @@ class Engine:
         return dict(value=tr(v), log_prior=tr(lp), ll=L.T.copy(), mu=m.T.copy(),
                     s2=s.T.copy(), scale=tr(sc))
 
+    def log_prior(self):
+        """[C, P, G]: the log priors as the reference holds them after the last iteration
+        (nmc_get_log_prior) -- under partial pooling each value's normal log density under the
+        current hyper-parameters, where get_state()["log_prior"] is the device's copy under
+        the hyper-parameters of the step that decided the value."""
+        lp = numpy.empty((self.P, self.G, self.C))
+        check(self.lib.nmc_get_log_prior(self.h, dptr(lp)))
+        return numpy.ascontiguousarray(numpy.transpose(lp, (2, 0, 1)))
+
     def set_replay(self, z, u, hz, hu):
         """z, u: [C, iter, P, G]; hz, hu: [C, iter, P] -> device [iter][P][G][C]."""
         zz = numpy.ascontiguousarray(numpy.transpose(z, (1, 2, 3, 0)), dtype=float)

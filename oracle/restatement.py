@@ -250,7 +250,8 @@ def run(nested, state, pooling, priors, n_iter, burn, thin, rng, *,
     """Sampler._loop restated for C chains in lockstep.
 
     ``priors``: list of scipy frozen distributions (none/complete pooling).
-    ``trace``:  optional dict collecting acc/llprop/lpprop/u per (iter, p).
+    ``trace``:  optional dict collecting acc/llprop/lpprop/margin/branch per (iter, p) and
+                the scales before and after every tuning.
     ``record``: optional list receiving (iteration, rows[C][cols]) at record iterations.
     """
     st = state
@@ -293,9 +294,15 @@ def run(nested, state, pooling, priors, n_iter, burn, thin, rng, *,
                 trace.setdefault("margin", []).append(
                     numpy.where(b4, numpy.abs(numpy.log(numpy.where(b4, u, 1.0)) - diff),
                                 numpy.inf))
+                # which of the four branches of :347-364 decided the step
+                trace.setdefault("branch", []).append(
+                    (1 * b1 + 2 * b2 + 3 * b3 + 4 * b4).astype(numpy.int8))
             if do_tune:
+                old = st.scale[:, p, :].copy() if trace is not None else None
                 st.scale[:, p, :], st.nacc[:, p, :], st.nrej[:, p, :] = tune(
                     st.scale[:, p, :], st.nacc[:, p, :], st.nrej[:, p, :])
+                if trace is not None:   # (iteration, parameter, scale before, scale after)
+                    trace.setdefault("tune", []).append((i, p, old, st.scale[:, p, :].copy()))
             if partial:
                 x = st.value[:, p, :]
                 mu_hat = numpy.array([pairwise_sum(x[c]) / G for c in range(C)])

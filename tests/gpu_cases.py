@@ -95,7 +95,8 @@ def run_engine(fam, sizes, st, sel, chain_base, n_iter, seed, pooling="partial",
     (accept flags [C, iter, P, G], proposal LLs, recorded rows [C, rows, cols], launch config).
     calls: the engine calls in order, ("run" | "prefill", i0, i1), ("synchronize", 0, 0),
     ("sleep", ms, 0) or ("get_state", 0, 0) (default: one run).  resident: nmc_set_resident
-    (launch config: "resident" stats, "state" the final get_state, "accept" the counts).
+    (launch config: "resident" stats, "state" the final get_state, "log_prior" the final
+    Engine.log_prior(), "accept" the counts).
     scale: proposal scales [C, P, G] of all chains of ``st`` (default: the engine's ones)."""
     import os
     from nestmc.engine import Engine
@@ -141,6 +142,7 @@ def run_engine(fam, sizes, st, sel, chain_base, n_iter, seed, pooling="partial",
     cfg["prefill"] = eng.prefill_stats()
     cfg["resident"] = res
     cfg["state"] = eng.get_state()
+    cfg["log_prior"] = eng.log_prior()
     cfg["accept"] = eng.accept_counts()
     eng.close()
     return acc, llp, rows, cfg
@@ -150,6 +152,14 @@ def run_oracle(nested, st, sel, chain_ids, n_iter, seed, pooling="partial", prio
                burn=None, thin=1, tune_interval=5, scale=None):
     """The numpy oracle on the same Philox stream for chains ``sel`` (global ids chain_ids);
     scale: proposal scales [C, P, G] of all chains of ``st`` (default ones)."""
+    return run_oracle_state(nested, st, sel, chain_ids, n_iter, seed, pooling, priors, burn,
+                            thin, tune_interval, scale)[:4]
+
+
+def run_oracle_state(nested, st, sel, chain_ids, n_iter, seed, pooling="partial", priors=None,
+                     burn=None, thin=1, tune_interval=5, scale=None):
+    """run_oracle, and beside its four results the oracle's final State (of chains ``sel``)
+    and its trace dict (oracle.restatement.run)."""
     from oracle import restatement as rs
     C = len(sel)
     o = rs.State(st.value[sel].copy(), st.lp[sel].copy(), st.ll[sel].copy(),
@@ -166,4 +176,4 @@ def run_oracle(nested, st, sel, chain_ids, n_iter, seed, pooling="partial", prio
     llp = numpy.stack(trace["llp"], 1).reshape(C, n_iter, P, G)
     margin = numpy.min(numpy.stack(trace["margin"]))
     rows = numpy.stack([r for _, r in rec], 1)
-    return acc, llp, rows, margin
+    return acc, llp, rows, margin, o, trace

@@ -12,7 +12,9 @@ and tests/test_rowpath_reference.py.
 """
 
 import collections
+import contextlib
 import functools
+import os
 
 import numpy
 import scipy.stats
@@ -394,3 +396,51 @@ def linreg1_fixed_order(y, b0):
         a4[u & 3] = a4[u & 3] + slots[u]
     acc = (a4[0] + a4[1]) + (a4[2] + a4[3])
     return -0.5 * (acc * 1.0) - float(n) * 0.9189385332046727
+
+
+# ---------------------------------------------------------------------------------------
+# helpers of the Gibbs geometry tests (tests/test_gpu_rowpaths.py, tests/test_gpu_gibbs_order.py)
+# ---------------------------------------------------------------------------------------
+@contextlib.contextmanager
+def environ(env):
+    """The environment variables ``env`` set while an Engine is created (NMC_* knobs)."""
+    old = {k: os.environ.get(k) for k in (env or {})}
+    os.environ.update(env or {})
+    try:
+        yield
+    finally:
+        for k, v in old.items():
+            if v is None:
+                os.environ.pop(k)
+            else:
+                os.environ[k] = v
+
+
+def gibbs_model(kind, G):
+    r = numpy.random.RandomState(1000 + G)
+    sizes = [int(s) for s in r.randint(16, 33, size=G)]
+    n = sum(sizes)
+    grp = numpy.repeat(numpy.arange(G), sizes)
+    if kind == "linreg2":
+        x = r.normal(size=n)
+        b0, b1 = r.normal(size=G), r.normal(2, 1, size=G)
+        y = b0[grp] + b1[grp] * x + r.normal(size=n)
+        return LinearRegression.simple(x, y, sigma=1.0), sizes
+    return GaussianMean.from_groups(r.normal(size=(1, G)), [0.8], sizes), sizes
+
+
+def gibbs_mode(fam, sizes):
+    """The step kernel and mode choose_geometry picks for partial pooling over G small groups
+    with rows in LDS: the register hand-off up to 64 groups, the Gibbs payload in LDS up to
+    128 while two payload buffers of G + 1 columns fit the CU's 160 KiB beside the carve
+    (P = 2: up to G = 120), nmc_k_run's all-wave update where they do not or where the
+    groups are more than four numpy leaves, nmc_k_sweep between."""
+    G, P = len(sizes), fam.n_params
+    if 128 < G and len(pairwise_leaves(G)) <= 4:
+        return "nmc_k_sweep<", ("NMC_MODE_SYNC_OWN",)
+    nacc = fam.n_fields if isinstance(fam, GaussianMean) else 1
+    doubles = max(sizes) * fam.n_fields
+    cols = carve_columns(nacc, P, True, G) + 2 * (G + 1) + (doubles + 63) // 64 + 1
+    if G <= 128 and cols * 512 <= 160 * 1024:
+        return "nmc_k_run<", ("NMC_MODE_SYNC_REG" if G <= 64 else "NMC_MODE_SYNC_LDS",)
+    return "nmc_k_run<", ("NMC_MODE_SYNC", "NMC_MODE_LAUNCH")

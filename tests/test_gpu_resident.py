@@ -31,9 +31,14 @@ PLANS = {
 def _same(a, b, what, partial=True):
     for k in range(3):
         assert numpy.array_equal(a[k], b[k], equal_nan=True), (what, k)
-    # (the hyper-parameters exist under partial pooling only)
-    for k in ("value", "log_prior", "ll", "scale") + (("mu", "s2") if partial else ()):
+    for k in ("value", "log_prior", "ll", "scale", "mu", "s2"):
         assert numpy.array_equal(a[3]["state"][k], b[3]["state"][k], equal_nan=True), (what, k)
+    # (the hyper-parameters exist under partial pooling only: NaN without, never whatever
+    #  the device buffers held)
+    for k in ("mu", "s2"):
+        assert numpy.isnan(a[3]["state"][k]).all() == (not partial), (what, k)
+        assert partial == bool(numpy.isfinite(a[3]["state"][k]).all()), (what, k)
+    assert numpy.array_equal(a[3]["log_prior"], b[3]["log_prior"], equal_nan=True), what
     assert numpy.array_equal(a[3]["accept"], b[3]["accept"]), what
 
 

@@ -42,35 +42,19 @@ a stale value instead.  Every staged case with odd n_fields failed tests 2 and 3
 clamp moved to the 16 bytes that hold the last double (rows.h nmc_ll_rows_staged).
 """
 
-import contextlib
-import os
-
 import numpy
 import pytest
 
 import rowpath_cases as rp
+from rowpath_cases import environ as _environ, gibbs_mode as _gibbs_mode, \
+    gibbs_model as _gibbs_model
 from gpu_cases import partial_state, run_engine, run_oracle
 from nestmc.engine import Engine
-from nestmc.families import GaussianMean, LinearRegression
 from oracle import restatement as rs
 
 pytestmark = pytest.mark.gpu
 
 C = 65      # one full chain block and a partly filled second one
-
-
-@contextlib.contextmanager
-def _environ(env):
-    old = {k: os.environ.get(k) for k in (env or {})}
-    os.environ.update(env or {})
-    try:
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k)
-            else:
-                os.environ[k] = v
 
 
 def _engine(case, n_chains, env=None, seed=0, chain_base=0):
@@ -246,36 +230,6 @@ def test_chain_matches_oracle(gpu_lib, name):
     assert numpy.allclose(llp[sel], ollp, rtol=1e-10, atol=1e-9, equal_nan=True)
     assert numpy.allclose(rows[sel], orows, rtol=1e-9, atol=1e-9, equal_nan=True)
     assert acc.mean() > 0.02
-
-
-def _gibbs_model(kind, G):
-    r = numpy.random.RandomState(1000 + G)
-    sizes = [int(s) for s in r.randint(16, 33, size=G)]
-    n = sum(sizes)
-    grp = numpy.repeat(numpy.arange(G), sizes)
-    if kind == "linreg2":
-        x = r.normal(size=n)
-        b0, b1 = r.normal(size=G), r.normal(2, 1, size=G)
-        y = b0[grp] + b1[grp] * x + r.normal(size=n)
-        return LinearRegression.simple(x, y, sigma=1.0), sizes
-    return GaussianMean.from_groups(r.normal(size=(1, G)), [0.8], sizes), sizes
-
-
-def _gibbs_mode(fam, sizes):
-    """The step kernel and mode choose_geometry picks for partial pooling over G small groups
-    with rows in LDS: the register hand-off up to 64 groups, the Gibbs payload in LDS up to
-    128 while two payload buffers of G + 1 columns fit the CU's 160 KiB beside the carve
-    (P = 2: up to G = 120), nmc_k_run's all-wave update where they do not or where the
-    groups are more than four numpy leaves, nmc_k_sweep between."""
-    G, P = len(sizes), fam.n_params
-    if 128 < G and len(rp.pairwise_leaves(G)) <= 4:
-        return "nmc_k_sweep<", ("NMC_MODE_SYNC_OWN",)
-    nacc = fam.n_fields if isinstance(fam, GaussianMean) else 1
-    doubles = max(sizes) * fam.n_fields
-    cols = rp.carve_columns(nacc, P, True, G) + 2 * (G + 1) + (doubles + 63) // 64 + 1
-    if G <= 128 and cols * 512 <= 160 * 1024:
-        return "nmc_k_run<", ("NMC_MODE_SYNC_REG" if G <= 64 else "NMC_MODE_SYNC_LDS",)
-    return "nmc_k_run<", ("NMC_MODE_SYNC", "NMC_MODE_LAUNCH")
 
 
 @pytest.mark.parametrize("G", [2, 3, 7, 8, 9, 63, 64, 65, 120, 121, 127, 128, 129, 136, 512,
