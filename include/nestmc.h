@@ -209,6 +209,21 @@ int nmc_write_ll_csvs(nmc_ctx* ctx, const char* dir, const int32_t* chain_ids, i
  * Event slots 14 and 15 bracket the kernel.                                      */
 int nmc_waic_partials(nmc_ctx* ctx, int row_begin, int n_rows, int n_valid, double* part,
                       int64_t* nonfinite);
+/* The convergence diagnostic's partial sums (Diagnostic, sampleDiagnosis.py:136-255: the split
+ * of every chain into two halves :136-155, the means and variances of :158-187, the variogram
+ * of :189-194) over recorded rows [row_begin, row_begin + n_rows) and local chains
+ * [0, n_valid), on the device from the sample store as it lies; n = n_rows / 2, half 0 = the
+ * window's rows [0, n), half 1 = rows [n, 2n).  Per (column k, chain c, half h), x the n values:
+ *   mean[k][h][c] = (x[0] + ... + x[n-1]) / n,  m2[k][h][c] = sum_q (x[q] - mean)^2,
+ *   S[t] = sum_{q < n-t} (x[q+t] - x[q])^2,  S[0] = 0          (all sums in row order)
+ * vg[CB][cols][n], CB = ceil(C / 64): per chain block, column and lag the block's 128 values
+ * S[t] added as a balanced tree over (chain, half), half minor (csrc/conv.h); not divided.
+ * Chains >= n_valid (a rank's padding) add +0.0 and their mean / m2 entries are +0.0.
+ * nestmc/convergence.py merges the blocks and finishes.  n_rows even and >= 4, the rows
+ * inside the schedule's, 1 <= n_valid <= C, else -1.  Event slots 12 and 13 bracket the
+ * kernel (nmc_waic_partials uses 14 and 15).                                      */
+int nmc_conv_partials(nmc_ctx* ctx, int row_begin, int n_rows, int n_valid, double* mean,
+                      double* m2, double* vg);
 
 /* Timing on the context's stream (hipEvents). */
 int nmc_event_record(nmc_ctx* ctx, int slot);                 /* slot 0..15 */

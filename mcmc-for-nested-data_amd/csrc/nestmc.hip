@@ -25,6 +25,7 @@
 
 #include "ctx.h"
 #include "kernels_misc.h"
+#include "conv.h"          // nmc_k_conv: convergence partials over the sample store
 
 #define NMC_VERSION "nestmc 0.2.0 (gfx950)"
 
@@ -1668,6 +1669,49 @@ int nmc_waic_partials(nmc_ctx* x, int row_begin, int n_rows, int n_valid, double
     if (e != hipSuccess) rc = fail(-2, std::string("waic_partials: ") + hipGetErrorString(e));
     *nonfinite = (int64_t)bad;
   }
+  hipFree(o);
+  return rc;
+}
+
+// The convergence diagnostic's partial sums (Diagnostic._computeBetween/WithinSequenceVariance
+// :158-187 and _computeVariogram :189-194 before their divisions) over the window's two halves
+// (:136-155), straight from the sample store (conv.h; include/nestmc.h).  The kernel does not
+// depend on the family.
+int nmc_conv_partials(nmc_ctx* x, int row_begin, int n_rows, int n_valid, double* mean,
+                      double* m2, double* vg) {
+  RES_PARK(x);
+  hipSetDevice(x->device);
+  const Dev& d = x->d;
+  if (n_rows < 4 || (n_rows & 1))
+    return fail(-1, "conv_partials: n_rows must be even and at least 4 (two halves of n >= 2)");
+  if (row_begin < 0 || row_begin > d.n_rows - n_rows)
+    return fail(-1, "conv_partials: row range out of bounds");
+  if (n_valid < 1 || n_valid > x->C) return fail(-1, "n_valid must be in 1..n_chains");
+  const int n = n_rows / 2, nlb = (n - 1 + NMC_CONV_L - 1) / NMC_CONV_L;
+  if (d.cols < 1 || ((int64_t)nlb + 1) * d.cols > 0x7fffffff || d.CB > 65535)
+    return fail(-1, "conv_partials: too many (column, lag block) tasks or chain blocks");
+  HIPCHK(hipStreamSynchronize(x->stream));
+  if (int rc = check_timeout(x)) return rc;
+  const size_t nv = (size_t)d.CB * d.cols * n, nm = (size_t)d.cols * 2 * x->C;
+  double* o = nullptr;
+  HIPCHK(hipMalloc(&o, (nv + 2 * nm) * 8));
+  int rc = nmc_event_record(x, 12);
+  hipError_t e = hipSuccess;
+  if (!rc) {
+    hipLaunchKernelGGL(nmc_k_conv, dim3((unsigned)((nlb + 1) * d.cols), d.CB), dim3(64), 0, x->stream,
+                       d.samples, x->C, d.cols, row_begin, n, n_valid, o, o + nv, o + nv + nm);
+    e = hipGetLastError();
+    if (e == hipSuccess) rc = nmc_event_record(x, 13);
+  }
+  if (!rc) {
+    if (e == hipSuccess) e = hipMemcpyAsync(vg, o, nv * 8, hipMemcpyDeviceToHost, x->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(mean, o + nv, nm * 8, hipMemcpyDeviceToHost, x->stream);
+    if (e == hipSuccess)
+      e = hipMemcpyAsync(m2, o + nv + nm, nm * 8, hipMemcpyDeviceToHost, x->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(x->stream);
+    if (e != hipSuccess) rc = fail(-2, std::string("conv_partials: ") + hipGetErrorString(e));
+  }
+  hipStreamSynchronize(x->stream);
   hipFree(o);
   return rc;
 }

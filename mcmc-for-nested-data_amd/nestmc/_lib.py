@@ -66,7 +66,9 @@ SIGNATURES = {
     "nmc_write_ll_csvs": (ctypes.c_int, [_vp, ctypes.c_char_p, _c_int32_p, ctypes.c_int]),
     "nmc_waic_partials": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                          _c_double_p, _c_int64_p]),
-    "nmc_event_record": (ctypes.c_int, [_vp, ctypes.c_int]),
+    "nmc_conv_partials": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                         _c_double_p, _c_double_p, _c_double_p]),
+    "nmc_event_record":(ctypes.c_int, [_vp, ctypes.c_int]),
     "nmc_event_elapsed": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int,
                                          ctypes.POINTER(ctypes.c_float)]),
     "nmc_set_kernel_timing": (ctypes.c_int, [_vp, ctypes.c_int]),

@@ -243,6 +243,37 @@ class Engine:
         parts = self.waic_partials(row_begin, n_rows, n_valid)
         return _waic.finish(_waic.merge(list(parts)), self.off)
 
+    def conv_partials(self, row_begin=0, n_rows=None, n_valid=None):
+        """The convergence diagnostic's partial sums over recorded rows [row_begin, row_begin +
+        n_rows) (n_rows even, two halves of n = n_rows / 2 >= 2 rows) and local chains
+        [0, n_valid), reduced on the device from the sample store (nmc_conv_partials;
+        nestmc.convergence): (vg [CB, cols, n], mean [cols, 2, C], m2 [cols, 2, C]).  Chains
+        from n_valid on (padding) add +0.0 to vg; their mean and m2 entries are +0.0."""
+        if n_rows is None:
+            n_rows = self.n_rows - row_begin
+        if n_valid is None:
+            n_valid = self.C
+        n_rows = int(n_rows)
+        n = max(n_rows // 2, 0)
+        vg = numpy.empty(((self.C + 63) // 64, self.cols, n))
+        mean = numpy.empty((self.cols, 2, self.C))
+        m2 = numpy.empty((self.cols, 2, self.C))
+        check(self.lib.nmc_conv_partials(self.h, int(row_begin), n_rows, int(n_valid),
+                                         dptr(mean), dptr(m2), dptr(vg)))
+        return vg, mean, m2
+
+    def convergence(self, names=None, row_begin=0, n_rows=None, n_valid=None):
+        """The ConvergenceResult (nestmc.convergence: rhat, effective n, mean, sd per column)
+        of this engine's chains over the given rows: its chain blocks' variogram sums merged
+        in chain-block order.  names: the columns' names (default "col<k>")."""
+        from . import convergence as _conv
+        vg, mean, m2 = self.conv_partials(row_begin, n_rows, n_valid)
+        nv = self.C if n_valid is None else int(n_valid)
+        if names is None:
+            names = ["col%d" % k for k in range(self.cols)]
+        return _conv.finish(_conv.merge(list(vg)), mean[:, :, :nv], m2[:, :, :nv],
+                            vg.shape[2], names)
+
     def eval_obs_ll(self):
         """Per-observation LL at the current state: [C, n_obs]."""
         out = numpy.empty((self.C, int(self.off[-1])))

@@ -23,6 +23,7 @@ import numpy
 
 from . import _lib
 from . import output
+from . import convergence as _conv
 from . import waic as _waic
 from .engine import Engine
 from .families import is_family
@@ -62,7 +63,7 @@ def sample_posterior(nChains, nIter, nSamples, parameterName, nGroups, nResponse
                      nProcesses=1, displayProgress=True, loggingLevel="info", *,
                      seed=0, devices=None, rng="philox", chains=None, return_samples=False,
                      write_files=True, replay=None, process_per_device=False, _rank=None,
-                     computeWaic=False):
+                     computeWaic=False, computeDiagnostics=False):
     """Drop-in for posteriorSampling.samplePosterior (same positional/keyword API).
 
     Extra keyword-only options (all optional):
@@ -86,6 +87,14 @@ def sample_posterior(nChains, nIter, nSamples, parameterName, nGroups, nResponse
                  GPU (nestmc.waic): outputDirectory/waic.csv and waic_pointwise.csv, and
                  "waic" (a nestmc.waic.WaicResult) in the returned dict; needs no
                  logLikelihood files, so saveLogLikelihood may be False
+      computeDiagnostics  after the loop, compute R-hat and the effective sample size of every
+                 column on the GPU from the device sample store (nestmc.convergence; the
+                 statistics of diagnoseSamples at full precision, without sample files):
+                 outputDirectory/convergence.csv, and "convergence" (a
+                 nestmc.convergence.ConvergenceResult) in the returned dict.  The recorded
+                 rows are cut into two halves: an odd number of them (or fewer than four)
+                 raises ValueError before sampling starts.  Median and HDI need a sort of
+                 every column's values and stay with diagnoseSamples
     nProcesses sizes the host threads used for chain initialisation and CSV writing.
     """
     start_time = datetime.datetime.now()
@@ -132,6 +141,11 @@ def sample_posterior(nChains, nIter, nSamples, parameterName, nGroups, nResponse
         print(msg)
 
     burn, thin = schedule(nIter, nSamples)
+    if computeDiagnostics:
+        n_rec = len(record_iterations(nIter, burn, thin))
+        if n_rec % 2 or n_rec < 4:
+            raise ValueError("computeDiagnostics cuts the %d recorded rows of a chain into two "
+                             "halves: their number must be even and at least 4" % n_rec)
     sizes = _sizes(nGroups, nResponsesPerGroup, pooling)
     G = len(sizes)
     priors = None
@@ -166,7 +180,7 @@ def sample_posterior(nChains, nIter, nSamples, parameterName, nGroups, nResponse
                   nProcesses=max(1, threads // len(devices)), displayProgress=displayProgress,
                   loggingLevel=loggingLevel, seed=seed, rng=rng,
                   return_samples=return_samples, write_files=write_files,
-                  computeWaic=computeWaic)
+                  computeWaic=computeWaic, computeDiagnostics=computeDiagnostics)
         res = ranks.run_per_device(kw, devices)
         _finish_log(logger, [], start_time, displayProgress)
         return res
@@ -245,7 +259,7 @@ def sample_posterior(nChains, nIter, nSamples, parameterName, nGroups, nResponse
                             write_files, sample_dir, threads, displayProgress, return_samples,
                             logger, chain_logs, start_time, rank_info,
                             compute_waic=bool(computeWaic), waic_dir=outputDirectory,
-                            n_real=nChains)
+                            n_real=nChains, compute_conv=bool(computeDiagnostics))
     finally:
         for eng, _, _ in engines:
             eng.close()
@@ -312,10 +326,49 @@ def _waic_of(engines, rank_info, n_real):
     return _waic.finish(part, off)
 
 
+def _conv_of(engines, rank_info, n_real, header):
+    """computeDiagnostics: every engine's partial sums over all recorded rows (its padding
+    chains, ids >= n_real, excluded); the chain blocks' variogram sums merged in engine order
+    and the half-chain moments concatenated in global chain order; the ranks of
+    process_per_device send theirs over the host group and rank 0 merges them in rank order
+    (the other ranks: None)."""
+    parts, means, m2s = [], [], []
+    eng0 = engines[0][0]
+    n = eng0.n_rows // 2
+    for eng, _, ids in engines:
+        n_valid = sum(1 for c in ids if c < n_real)
+        if n_valid > 0:
+            vg, mean, m2 = eng.conv_partials(n_valid=n_valid)
+            parts.extend(vg)
+            means.append(mean[:, :, :n_valid])
+            m2s.append(m2[:, :, :n_valid])
+        else:
+            parts.append(numpy.zeros((eng.cols, n)))
+    vg = _conv.merge(parts)
+    cols = eng0.cols
+    mean = numpy.concatenate(means, axis=2) if means else numpy.zeros((cols, 2, 0))
+    m2 = numpy.concatenate(m2s, axis=2) if m2s else numpy.zeros((cols, 2, 0))
+    if rank_info is not None:
+        buf = numpy.concatenate([vg.ravel(), mean.ravel(), m2.ravel()])
+        got = rank_info["hg"].gather(numpy.ascontiguousarray(buf).tobytes())
+        if rank_info["rank"] != 0:
+            return None
+        vgs, means, m2s = [], [], []
+        for b in got:
+            a = numpy.frombuffer(b, dtype=numpy.float64)
+            nv = (len(a) - cols * n) // (4 * cols)
+            vgs.append(a[:cols * n].reshape(cols, n))
+            means.append(a[cols * n:cols * n + 2 * cols * nv].reshape(cols, 2, nv))
+            m2s.append(a[cols * n + 2 * cols * nv:].reshape(cols, 2, nv))
+        vg = _conv.merge_ranks(vgs)
+        mean, m2 = numpy.concatenate(means, axis=2), numpy.concatenate(m2s, axis=2)
+    return _conv.finish(vg, mean, m2, n, header)
+
+
 def _sample_loop(engines, nIter, burn, thin, names, G, partial, saveLogLikelihood, write_files,
                  sample_dir, threads, displayProgress, return_samples, logger, chain_logs,
                  start_time, rank_info=None, compute_waic=False, waic_dir=None,
-                 n_real=None):
+                 n_real=None, compute_conv=False):
     """The device loop, the per-observation LL rows and the sample files of
     sample_posterior (the caller closes the engines whatever happens here).  rank_info: a
     rank of process_per_device -- this rank writes its chains' logLikelihood files, rank 0
@@ -358,8 +411,14 @@ def _sample_loop(engines, nIter, burn, thin, names, G, partial, saveLogLikelihoo
         if waic_result is not None and write_files:
             _waic.write_csvs(waic_result, waic_dir)
 
-    # ---- samples -> files ----------------------------------------------------
     header = output.header_names(names, G, partial)
+    conv_result = None
+    if compute_conv:
+        conv_result = _conv_of(engines, rank_info, n_real, header)
+        if conv_result is not None and write_files:
+            _conv.write_csv(conv_result, waic_dir)
+
+    # ---- samples -> files ----------------------------------------------------
     hdr = header if burn < nIter else None
     rows_all = []
     if rank_info is not None:
@@ -391,5 +450,7 @@ def _sample_loop(engines, nIter, burn, thin, names, G, partial, saveLogLikelihoo
                "loop_seconds": loop_seconds}
         if waic_result is not None:
             res["waic"] = waic_result
+        if conv_result is not None:
+            res["convergence"] = conv_result
         return res
     return None

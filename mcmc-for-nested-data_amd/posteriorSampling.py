@@ -24,14 +24,16 @@ def samplePosterior(nChains, nIter, nSamples,
                     priorDistribution=None,
                     startWithMLE=False, startingPointValueRange=None,
                     nProcesses=1, displayProgress=True, loggingLevel="info",
-                    computeWaic=False, **gpu_options):
+                    computeWaic=False, computeDiagnostics=False, **gpu_options):
     """Sample the posterior of a nested model; samples go to outputDirectory/sample/.
 
     Arguments mirror the reference (posteriorSampling.py:28-145).  Keyword-only
     GPU options: seed, devices, rng, chains, return_samples (nestmc.sampler).
     computeWaic=True also reduces the per-observation log-likelihood of the recorded rows
     to WAIC on the GPU (waic.csv, waic_pointwise.csv; nestmc.waic), with or without
-    saveLogLikelihood.  Returns None like the reference unless return_samples=True.
+    saveLogLikelihood.  computeDiagnostics=True also computes R-hat and the effective sample
+    size of every column on the GPU from the device sample store (convergence.csv;
+    nestmc.convergence) -- an even number of recorded rows is needed.  Returns None like the reference unless return_samples=True.
     """
     return sample_posterior(nChains, nIter, nSamples, parameterName, nGroups,
                             nResponsesPerGroup, pooling, logLikelihoodFunction,
@@ -40,4 +42,5 @@ def samplePosterior(nChains, nIter, nSamples,
                             startingPointValueRange=startingPointValueRange,
                             nProcesses=nProcesses, displayProgress=displayProgress,
                             loggingLevel=loggingLevel, computeWaic=computeWaic,
+                            computeDiagnostics=computeDiagnostics,
                             **gpu_options)
