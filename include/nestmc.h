@@ -224,6 +224,32 @@ int nmc_waic_partials(nmc_ctx* ctx, int row_begin, int n_rows, int n_valid, doub
  * kernel (nmc_waic_partials uses 14 and 15).                                      */
 int nmc_conv_partials(nmc_ctx* ctx, int row_begin, int n_rows, int n_valid, double* mean,
                       double* m2, double* vg);
+/* The order statistics of every column of the sample store (the median and HDI of
+ * Diagnostic._computeMedianAndHdi, sampleDiagnosis.py:419-427, and computeHpdInterval
+ * :766-776) over recorded rows [row_begin, row_begin + n_rows) and local chains [0, n_valid),
+ * on the device from the store as it lies: a column's N = n_rows * n_valid values are sorted
+ * (csrc/sortcol.h: tiles of 4096 keys in LDS, then merge passes) by the key that orders a
+ * double's bits like the number (-inf < ... < -0.0 < +0.0 < ... < +inf < +NaN), s the result:
+ *   at_ranks[col][r] = s[ranks[r]]                      (n_ranks may be 0, at_ranks then unused)
+ *   hdi[col]         = (s[i], s[i + gap]), hdi_at[col] = i, the first i in [0, N - gap) that
+ *                      minimises s[i + gap] - s[i]      (one fp64 subtraction per i)
+ *   nonfinite[col]   = the column's values that are NaN or +-inf; such a column gets NaN for
+ *                      every statistic and hdi_at = -1
+ *   sorted           = NULL, or [cols][N]: every column in key order
+ * All of it depends on the multiset of a column's values alone.  Columns are sorted in batches
+ * whose temporary buffers (2 * batch * N * 8 bytes, allocated and freed by the call) fit
+ * 1 GiB; col_batch > 0 sets the columns per batch.  The rows inside the schedule's,
+ * 1 <= n_valid <= C, 2 <= N < 2^31, 1 <= gap <= N - 1, 0 <= ranks[r] <= N - 1, else -1.
+ * Event slots 10 and 11 bracket the kernels.                                       */
+int nmc_summary(nmc_ctx* ctx, int row_begin, int n_rows, int n_valid, int64_t gap,
+                const int64_t* ranks, int n_ranks, int col_batch, double* at_ranks, double* hdi,
+                int64_t* hdi_at, int64_t* nonfinite, double* sorted);
+/* The same over a host array x[rows][cols][C] in the store's layout (all of its rows), copied
+ * to `device`; needs no context.                                                      */
+int nmc_summary_of(int device, const double* x, int rows, int cols, int C, int n_valid,
+                   int64_t gap, const int64_t* ranks, int n_ranks, int col_batch,
+                   double* at_ranks, double* hdi, int64_t* hdi_at, int64_t* nonfinite,
+                   double* sorted);
 
 /* Timing on the context's stream (hipEvents). */
 int nmc_event_record(nmc_ctx* ctx, int slot);                 /* slot 0..15 */

@@ -26,6 +26,7 @@
 #include "ctx.h"
 #include "kernels_misc.h"
 #include "conv.h"          // nmc_k_conv: convergence partials over the sample store
+#include "sortcol.h"       // nmc_k_sort_*: the columns' sort and order statistics
 
 #define NMC_VERSION "nestmc 0.2.0 (gfx950)"
 
@@ -1713,6 +1714,139 @@ int nmc_conv_partials(nmc_ctx* x, int row_begin, int n_rows, int n_valid, double
   }
   hipStreamSynchronize(x->stream);
   hipFree(o);
+  return rc;
+}
+
+// The order statistics of every column of a store [rows][cols][C] on the device (sortcol.h;
+// include/nestmc.h): the median's and any other ranks, the HDI of computeHpdInterval
+// (sampleDiagnosis.py:766-776) and, on request, the sorted columns.  Columns go in batches
+// whose two key buffers fit 1 GiB (the variate buffers' figure), or of col_batch columns.
+static int summary_check(int rows, int C, int cols, int row_begin, int n_rows, int n_valid,
+                         int64_t gap, const int64_t* ranks, int n_ranks, int col_batch) {
+  if (cols < 1) return fail(-1, "summary: no columns");
+  if (n_rows < 1 || row_begin < 0 || row_begin > rows - n_rows)
+    return fail(-1, "summary: row range out of bounds");
+  if (n_valid < 1 || n_valid > C) return fail(-1, "n_valid must be in 1..n_chains");
+  const int64_t N = (int64_t)n_rows * n_valid;
+  if (N < 2) return fail(-1, "summary: a column needs at least two values");
+  if (N >= ((int64_t)1 << 31)) return fail(-1, "summary: 2^31 or more values per column");
+  if (gap < 1 || gap > N - 1) return fail(-1, "summary: gap must be in 1..N-1");
+  if (n_ranks < 0 || (n_ranks > 0 && !ranks) || col_batch < 0)
+    return fail(-1, "summary: n_ranks and col_batch must not be negative");
+  for (int r = 0; r < n_ranks; ++r)
+    if (ranks[r] < 0 || ranks[r] > N - 1) return fail(-1, "summary: a rank outside 0..N-1");
+  return 0;
+}
+
+// x: the context whose event slots 10 / 11 bracket the kernels, or NULL.
+static int summary_run(nmc_ctx* x, hipStream_t st, const double* samples, int C, int cols,
+                       int row_begin, int n_rows, int n_valid, int64_t gap, const int64_t* ranks,
+                       int n_ranks, int col_batch, double* at_ranks, double* hdi,
+                       int64_t* hdi_at, int64_t* nonfinite, double* sorted) {
+  const int64_t N = (int64_t)n_rows * n_valid;
+  const int64_t tiles = (N + NMC_SORT_TILE - 1) / NMC_SORT_TILE;
+  const size_t budget = (size_t)1 << 30;
+  int64_t kb = col_batch > 0 ? col_batch : (int64_t)(budget / ((size_t)N * 16));
+  kb = std::max<int64_t>(1, std::min<int64_t>({kb, (int64_t)cols, (int64_t)65535}));
+  uint64_t* buf[2] = {nullptr, nullptr};
+  int64_t* d_ranks = nullptr;
+  double *d_at = nullptr, *d_hdi = nullptr;
+  int64_t* d_hat = nullptr;
+  unsigned long long* d_bad = nullptr;
+  auto cleanup = [&]() {
+    hipStreamSynchronize(st);
+    hipFree(buf[0]); hipFree(buf[1]); hipFree(d_ranks); hipFree(d_at); hipFree(d_hdi);
+    hipFree(d_hat); hipFree(d_bad);
+  };
+  const size_t nr = (size_t)(n_ranks ? n_ranks : 1);
+  hipError_t e = hipMalloc(&buf[0], (size_t)kb * N * 8);
+  if (e == hipSuccess) e = hipMalloc(&buf[1], (size_t)kb * N * 8);
+  if (e == hipSuccess) e = hipMalloc(&d_ranks, nr * 8);
+  if (e == hipSuccess) e = hipMalloc(&d_at, (size_t)cols * nr * 8);
+  if (e == hipSuccess) e = hipMalloc(&d_hdi, (size_t)cols * 16);
+  if (e == hipSuccess) e = hipMalloc(&d_hat, (size_t)cols * 8);
+  if (e == hipSuccess) e = hipMalloc(&d_bad, (size_t)cols * 8);
+  if (e == hipSuccess && n_ranks)
+    e = hipMemcpyAsync(d_ranks, ranks, nr * 8, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemsetAsync(d_bad, 0, (size_t)cols * 8, st);
+  int rc = 0;
+  if (e == hipSuccess && x) rc = nmc_event_record(x, 10);
+  for (int c0 = 0; c0 < cols && e == hipSuccess && !rc; c0 += (int)kb) {
+    const int k = (int)std::min<int64_t>(kb, cols - c0);
+    const dim3 grid((unsigned)tiles, (unsigned)k);
+    hipLaunchKernelGGL(nmc_k_sort_tiles, grid, dim3(NMC_SORT_THREADS), 0, st, samples, C, cols,
+                       row_begin, n_valid, N, c0, buf[0], d_bad);
+    e = hipGetLastError();
+    int cur = 0;
+    for (int64_t L = NMC_SORT_TILE; L < N && e == hipSuccess; L *= 2, cur ^= 1) {
+      hipLaunchKernelGGL(nmc_k_sort_merge, grid, dim3(NMC_SORT_THREADS), 0, st, buf[cur],
+                         buf[cur ^ 1], N, L);
+      e = hipGetLastError();
+    }
+    if (e == hipSuccess) {
+      hipLaunchKernelGGL(nmc_k_sort_scan, dim3((unsigned)k), dim3(NMC_SORT_THREADS), 0, st,
+                         buf[cur], N, gap, d_ranks, n_ranks, c0, d_bad, d_at, d_hdi, d_hat);
+      e = hipGetLastError();
+    }
+    if (e == hipSuccess && sorted)
+      e = hipMemcpyAsync(sorted + (size_t)c0 * N, buf[cur], (size_t)k * N * 8,
+                         hipMemcpyDeviceToHost, st);
+  }
+  if (e == hipSuccess && !rc && x) rc = nmc_event_record(x, 11);
+  if (e == hipSuccess && !rc && n_ranks)
+    e = hipMemcpyAsync(at_ranks, d_at, (size_t)cols * nr * 8, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess && !rc) e = hipMemcpyAsync(hdi, d_hdi, (size_t)cols * 16, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess && !rc) e = hipMemcpyAsync(hdi_at, d_hat, (size_t)cols * 8, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess && !rc)
+    e = hipMemcpyAsync(nonfinite, d_bad, (size_t)cols * 8, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess && !rc) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) rc = fail(-2, std::string("summary: ") + hipGetErrorString(e));
+  cleanup();
+  if (!rc && sorted) {   // the keys' inverse, on the copy
+    uint64_t* w = reinterpret_cast<uint64_t*>(sorted);
+    for (size_t i = 0, n = (size_t)cols * N; i < n; ++i) w[i] = nmc_sort_unkey(w[i]);
+  }
+  return rc;
+}
+
+int nmc_summary(nmc_ctx* x, int row_begin, int n_rows, int n_valid, int64_t gap,
+                const int64_t* ranks, int n_ranks, int col_batch, double* at_ranks, double* hdi,
+                int64_t* hdi_at, int64_t* nonfinite, double* sorted) {
+  RES_PARK(x);
+  hipSetDevice(x->device);
+  const Dev& d = x->d;
+  if (int rc = summary_check(d.n_rows, x->C, d.cols, row_begin, n_rows, n_valid, gap, ranks,
+                             n_ranks, col_batch))
+    return rc;
+  HIPCHK(hipStreamSynchronize(x->stream));
+  if (int rc = check_timeout(x)) return rc;
+  return summary_run(x, x->stream, d.samples, x->C, d.cols, row_begin, n_rows, n_valid, gap,
+                     ranks, n_ranks, col_batch, at_ranks, hdi, hdi_at, nonfinite, sorted);
+}
+
+int nmc_summary_of(int device, const double* xs, int rows, int cols, int C, int n_valid,
+                   int64_t gap, const int64_t* ranks, int n_ranks, int col_batch,
+                   double* at_ranks, double* hdi, int64_t* hdi_at, int64_t* nonfinite,
+                   double* sorted) {
+  if (rows < 1 || C < 1) return fail(-1, "summary_of: need rows >= 1 and C >= 1");
+  const int row_begin = 0, n_rows = rows;   // (the whole array is the window)
+  if (int rc = summary_check(rows, C, cols, row_begin, n_rows, n_valid, gap, ranks, n_ranks,
+                             col_batch))
+    return rc;
+  HIPCHK(hipSetDevice(device));
+  hipStream_t st;
+  HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+  double* dx = nullptr;
+  const size_t nx = (size_t)rows * cols * C;
+  hipError_t e = hipMalloc(&dx, nx * 8);
+  if (e == hipSuccess) e = hipMemcpyAsync(dx, xs, nx * 8, hipMemcpyHostToDevice, st);
+  int rc = e == hipSuccess
+               ? summary_run(nullptr, st, dx, C, cols, row_begin, n_rows, n_valid, gap, ranks,
+                             n_ranks, col_batch, at_ranks, hdi, hdi_at, nonfinite, sorted)
+               : fail(-2, std::string("summary_of: ") + hipGetErrorString(e));
+  hipStreamSynchronize(st);
+  hipFree(dx);
+  hipStreamDestroy(st);
   return rc;
 }
 

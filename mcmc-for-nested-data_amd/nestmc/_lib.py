@@ -68,6 +68,14 @@ SIGNATURES = {
                                          _c_double_p, _c_int64_p]),
     "nmc_conv_partials": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                          _c_double_p, _c_double_p, _c_double_p]),
+    "nmc_summary": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                   ctypes.c_int64, _c_int64_p, ctypes.c_int, ctypes.c_int,
+                                   _c_double_p, _c_double_p, _c_int64_p, _c_int64_p,
+                                   _c_double_p]),
+    "nmc_summary_of": (ctypes.c_int, [ctypes.c_int, _c_double_p, ctypes.c_int, ctypes.c_int,
+                                      ctypes.c_int, ctypes.c_int, ctypes.c_int64, _c_int64_p,
+                                      ctypes.c_int, ctypes.c_int, _c_double_p, _c_double_p,
+                                      _c_int64_p, _c_int64_p, _c_double_p]),
     "nmc_event_record":(ctypes.c_int, [_vp, ctypes.c_int]),
     "nmc_event_elapsed": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int,
                                          ctypes.POINTER(ctypes.c_float)]),

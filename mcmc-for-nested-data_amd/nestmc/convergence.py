@@ -23,7 +23,8 @@ var and nestmc.diagnosis.variogram.  Both diagnose the chains at full precision,
 diagnoseSamples reads them back from files of six decimals.
 
 The median and the 95 % HDI of diagnoseSamples need a sort of all m n values of a column:
-they stay with diagnoseSamples and are not computed here.
+nestmc.summary (Engine.summary, samplePosterior(computeSummary=True)) computes them from the
+store, and nestmc.summary.assessment joins the two results into Diagnostic's table.
 
 This module is numpy only and imports without a GPU (from_halfchains calls the GPU unless it
 is given ``variogram=variogram_host``).

@@ -274,6 +274,49 @@ class Engine:
         return _conv.finish(_conv.merge(list(vg)), mean[:, :, :nv], m2[:, :, :nv],
                             vg.shape[2], names)
 
+    def summary_raw(self, row_begin=0, n_rows=None, n_valid=None, hdi_p=95, ranks=None,
+                    col_batch=0, want_sorted=False):
+        """The order statistics of every column over recorded rows [row_begin, row_begin +
+        n_rows) and local chains [0, n_valid), N = n_rows * n_valid values each, sorted on the
+        device from the sample store (nmc_summary; nestmc.summary): a dict of at_ranks
+        [cols, len(ranks)] (the sorted column at ``ranks``; default
+        nestmc.summary.stat_ranks(N): the median's two, the minimum's, the maximum's), hdi
+        [cols, 2] and hdi_at [cols] (the hdi_p % interval and the rank of its lower end),
+        nonfinite [cols] (a column with NaN or infinite values has NaN statistics and hdi_at
+        -1), sorted ([cols, N], every column in key order, with want_sorted; else None), N and
+        gap.  col_batch: the columns sorted at a time (0: what fits the 1 GiB of temporary
+        buffers)."""
+        from . import summary as _summary
+        if n_rows is None:
+            n_rows = self.n_rows - row_begin
+        if n_valid is None:
+            n_valid = self.C
+        n_rows, n_valid = int(n_rows), int(n_valid)
+        N = n_rows * n_valid
+        if N < 2:
+            raise ValueError("a summary needs at least two values per column (got %d)" % N)
+        gap = _summary.gap_of(N, hdi_p)
+        rk = numpy.ascontiguousarray(_summary.stat_ranks(N) if ranks is None else ranks,
+                                     dtype=numpy.int64).reshape(-1)
+        i64 = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))   # noqa: E731
+        at = numpy.empty((self.cols, len(rk)))
+        hdi = numpy.empty((self.cols, 2))
+        hdi_at = numpy.empty(self.cols, dtype=numpy.int64)
+        bad = numpy.empty(self.cols, dtype=numpy.int64)
+        srt = numpy.empty((self.cols, N)) if want_sorted else None
+        check(self.lib.nmc_summary(self.h, int(row_begin), n_rows, n_valid, gap, i64(rk),
+                                   len(rk), int(col_batch), dptr(at), dptr(hdi), i64(hdi_at),
+                                   i64(bad), dptr(srt)))
+        return dict(at_ranks=at, hdi=hdi, hdi_at=hdi_at, nonfinite=bad, sorted=srt, N=N, gap=gap)
+
+    def summary(self, names=None, row_begin=0, n_rows=None, n_valid=None, hdi_p=95, col_batch=0):
+        """The SummaryResult (nestmc.summary: median, HDI, minimum, maximum per column) of this
+        engine's chains over the given rows.  names: the columns' names (default "col<k>")."""
+        from . import summary as _summary
+        raw = self.summary_raw(row_begin, n_rows, n_valid, hdi_p, None, col_batch)
+        return _summary.finish(raw["at_ranks"], raw["hdi"], raw["nonfinite"], raw["N"], names,
+                               hdi_p)
+
     def eval_obs_ll(self):
         """Per-observation LL at the current state: [C, n_obs]."""
         out = numpy.empty((self.C, int(self.off[-1])))

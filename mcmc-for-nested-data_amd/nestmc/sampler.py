@@ -24,6 +24,7 @@ import numpy
 from . import _lib
 from . import output
 from . import convergence as _conv
+from . import summary as _summary
 from . import waic as _waic
 from .engine import Engine
 from .families import is_family
@@ -63,7 +64,7 @@ def sample_posterior(nChains, nIter, nSamples, parameterName, nGroups, nResponse
                      nProcesses=1, displayProgress=True, loggingLevel="info", *,
                      seed=0, devices=None, rng="philox", chains=None, return_samples=False,
                      write_files=True, replay=None, process_per_device=False, _rank=None,
-                     computeWaic=False, computeDiagnostics=False):
+                     computeWaic=False, computeDiagnostics=False, computeSummary=False):
     """Drop-in for posteriorSampling.samplePosterior (same positional/keyword API).
 
     Extra keyword-only options (all optional):
@@ -93,8 +94,18 @@ def sample_posterior(nChains, nIter, nSamples, parameterName, nGroups, nResponse
                  outputDirectory/convergence.csv, and "convergence" (a
                  nestmc.convergence.ConvergenceResult) in the returned dict.  The recorded
                  rows are cut into two halves: an odd number of them (or fewer than four)
-                 raises ValueError before sampling starts.  Median and HDI need a sort of
-                 every column's values and stay with diagnoseSamples
+                 raises ValueError before sampling starts.  Median and HDI: computeSummary
+      computeSummary  after the loop, sort every column of the device sample store on the GPU
+                 and take its median, 95 % HDI, minimum and maximum (nestmc.summary; the
+                 numbers of diagnoseSamples at full precision, without sample files):
+                 outputDirectory/summary.csv, and "summary" (a nestmc.summary.SummaryResult)
+                 in the returned dict; with computeDiagnostics as well also "assessment", the
+                 table of Diagnostic.assessment.  With one engine only per-column results
+                 leave the device; several engines (devices=[...]) and the ranks of
+                 process_per_device each sort their own chains' values and rank 0 merges the
+                 sorted columns on the host -- as many bytes as the sample gather those paths
+                 already do.  Fewer than two values per column raise ValueError before
+                 sampling starts
     nProcesses sizes the host threads used for chain initialisation and CSV writing.
     """
     start_time = datetime.datetime.now()
@@ -146,6 +157,12 @@ def sample_posterior(nChains, nIter, nSamples, parameterName, nGroups, nResponse
         if n_rec % 2 or n_rec < 4:
             raise ValueError("computeDiagnostics cuts the %d recorded rows of a chain into two "
                              "halves: their number must be even and at least 4" % n_rec)
+    if computeSummary:
+        n_val = len(record_iterations(nIter, burn, thin)) * \
+            (nChains if chains is None else len(chains))
+        if n_val < 2:
+            raise ValueError("computeSummary needs at least two values per column: the "
+                             "recorded rows of all chains give %d" % n_val)
     sizes = _sizes(nGroups, nResponsesPerGroup, pooling)
     G = len(sizes)
     priors = None
@@ -180,7 +197,8 @@ def sample_posterior(nChains, nIter, nSamples, parameterName, nGroups, nResponse
                   nProcesses=max(1, threads // len(devices)), displayProgress=displayProgress,
                   loggingLevel=loggingLevel, seed=seed, rng=rng,
                   return_samples=return_samples, write_files=write_files,
-                  computeWaic=computeWaic, computeDiagnostics=computeDiagnostics)
+                  computeWaic=computeWaic, computeDiagnostics=computeDiagnostics,
+                  computeSummary=computeSummary)
         res = ranks.run_per_device(kw, devices)
         _finish_log(logger, [], start_time, displayProgress)
         return res
@@ -259,7 +277,8 @@ def sample_posterior(nChains, nIter, nSamples, parameterName, nGroups, nResponse
                             write_files, sample_dir, threads, displayProgress, return_samples,
                             logger, chain_logs, start_time, rank_info,
                             compute_waic=bool(computeWaic), waic_dir=outputDirectory,
-                            n_real=nChains, compute_conv=bool(computeDiagnostics))
+                            n_real=nChains, compute_conv=bool(computeDiagnostics),
+                            compute_summary=bool(computeSummary))
     finally:
         for eng, _, _ in engines:
             eng.close()
@@ -365,10 +384,40 @@ def _conv_of(engines, rank_info, n_real, header):
     return _conv.finish(vg, mean, m2, n, header)
 
 
+def _summary_of(engines, rank_info, n_real, header):
+    """computeSummary: one engine sorts its store's columns and only per-column results leave
+    the device.  Several engines, and the ranks of process_per_device, each sort the values of
+    their own real chains (padding chains, ids >= n_real, excluded) and hand over the sorted
+    columns -- as many bytes as the sample gather; the engines' columns are merged here, the
+    ranks' on rank 0 after a gather over the host group (the other ranks: None).  Order
+    statistics depend on the multiset alone: the result is the one engine's, bit for bit."""
+    if len(engines) == 1 and rank_info is None:
+        eng, _, ids = engines[0]
+        return eng.summary(header, n_valid=sum(1 for c in ids if c < n_real))
+    cols = engines[0][0].cols
+    parts = []
+    for eng, _, ids in engines:
+        n_valid = sum(1 for c in ids if c < n_real)
+        if n_valid * eng.n_rows >= 2:
+            parts.append(eng.summary_raw(n_valid=n_valid, want_sorted=True)["sorted"])
+        elif n_valid > 0:       # (a single value per column: nothing to sort)
+            parts.append(eng.samples_raw()[:, :, 0].T)
+        else:
+            parts.append(numpy.empty((cols, 0)))
+    part = _summary.merge_sorted(parts)
+    if rank_info is not None:
+        got = rank_info["hg"].gather(numpy.ascontiguousarray(part).tobytes())
+        if rank_info["rank"] != 0:
+            return None
+        part = _summary.merge_sorted([numpy.frombuffer(b, dtype=numpy.float64).reshape(cols, -1)
+                                      for b in got])
+    return _summary.from_sorted(part, header)
+
+
 def _sample_loop(engines, nIter, burn, thin, names, G, partial, saveLogLikelihood, write_files,
                  sample_dir, threads, displayProgress, return_samples, logger, chain_logs,
                  start_time, rank_info=None, compute_waic=False, waic_dir=None,
-                 n_real=None, compute_conv=False):
+                 n_real=None, compute_conv=False, compute_summary=False):
     """The device loop, the per-observation LL rows and the sample files of
     sample_posterior (the caller closes the engines whatever happens here).  rank_info: a
     rank of process_per_device -- this rank writes its chains' logLikelihood files, rank 0
@@ -417,6 +466,11 @@ def _sample_loop(engines, nIter, burn, thin, names, G, partial, saveLogLikelihoo
         conv_result = _conv_of(engines, rank_info, n_real, header)
         if conv_result is not None and write_files:
             _conv.write_csv(conv_result, waic_dir)
+    summary_result = None
+    if compute_summary:
+        summary_result = _summary_of(engines, rank_info, n_real, header)
+        if summary_result is not None and write_files:
+            _summary.write_csv(summary_result, waic_dir)
 
     # ---- samples -> files ----------------------------------------------------
     hdr = header if burn < nIter else None
@@ -452,5 +506,9 @@ def _sample_loop(engines, nIter, burn, thin, names, G, partial, saveLogLikelihoo
             res["waic"] = waic_result
         if conv_result is not None:
             res["convergence"] = conv_result
+        if summary_result is not None:
+            res["summary"] = summary_result
+            if conv_result is not None:
+                res["assessment"] = _summary.assessment(conv_result, summary_result)
         return res
     return None

@@ -24,7 +24,8 @@ def samplePosterior(nChains, nIter, nSamples,
                     priorDistribution=None,
                     startWithMLE=False, startingPointValueRange=None,
                     nProcesses=1, displayProgress=True, loggingLevel="info",
-                    computeWaic=False, computeDiagnostics=False, **gpu_options):
+                    computeWaic=False, computeDiagnostics=False, computeSummary=False,
+                    **gpu_options):
     """Sample the posterior of a nested model; samples go to outputDirectory/sample/.
 
     Arguments mirror the reference (posteriorSampling.py:28-145).  Keyword-only
@@ -33,7 +34,10 @@ def samplePosterior(nChains, nIter, nSamples,
     to WAIC on the GPU (waic.csv, waic_pointwise.csv; nestmc.waic), with or without
     saveLogLikelihood.  computeDiagnostics=True also computes R-hat and the effective sample
     size of every column on the GPU from the device sample store (convergence.csv;
-    nestmc.convergence) -- an even number of recorded rows is needed.  Returns None like the reference unless return_samples=True.
+    nestmc.convergence) -- an even number of recorded rows is needed.  computeSummary=True
+    also sorts every column of the store on the GPU for its median, 95 % HDI, minimum and
+    maximum (summary.csv; nestmc.summary).  Returns None like the reference unless
+    return_samples=True.
     """
     return sample_posterior(nChains, nIter, nSamples, parameterName, nGroups,
                             nResponsesPerGroup, pooling, logLikelihoodFunction,
@@ -43,4 +47,5 @@ def samplePosterior(nChains, nIter, nSamples,
                             nProcesses=nProcesses, displayProgress=displayProgress,
                             loggingLevel=loggingLevel, computeWaic=computeWaic,
                             computeDiagnostics=computeDiagnostics,
+                            computeSummary=computeSummary,
                             **gpu_options)
