@@ -250,6 +250,32 @@ int nmc_summary_of(int device, const double* x, int rows, int cols, int C, int n
                    int64_t gap, const int64_t* ranks, int n_ranks, int col_batch,
                    double* at_ranks, double* hdi, int64_t* hdi_at, int64_t* nonfinite,
                    double* sorted);
+/* PSIS-LOO (Vehtari, Gelman, Gabry 2017) of every observation over recorded rows [row_begin,
+ * row_begin + n_rows) and local chains [0, n_valid), on the device from the sample store; the
+ * definitions are nestmc/loo.py's docstring.  Observations go in batches: the batch's
+ * per-observation log-likelihoods (the values of nmc_obs_ll_rows, bit for bit) are written in
+ * the store's layout [n_rows][batch][C] (nmc_k_loo_ll), their columns sorted by the kernels of
+ * nmc_summary, and one workgroup per observation fits and smooths the tail of its sorted
+ * column (csrc/psis.h).  Per observation i:
+ *   elpd_i[i], lppd_i[i]  the leave-one-out and the plain log pointwise predictive density
+ *   k_i[i]                the Pareto shape estimate; +inf when the tail has 4 values or fewer
+ *   n_tail_i[i]           the values strictly above the cutoff, <= M = ceil(min(S/5, 3 sqrt(S)))
+ *   nonfinite_i[i]        its log-likelihoods that are NaN or +-inf; such an observation gets
+ *                         NaN for elpd, lppd and k and n_tail 0
+ * with S = n_rows * n_valid.  All of it depends on the multiset of an observation's values
+ * alone: batches and row ranges change no bit.  The three temporary buffers of a batch (the
+ * log-likelihoods and two key buffers, allocated and freed by the call) fit 1 GiB; obs_batch > 0
+ * sets the observations per batch.  The rows inside the schedule's, 1 <= n_valid <= C,
+ * 2 <= S < 2^31, M <= 8191 (S up to about 7.4e6), obs_batch >= 0, else -1 and nothing is
+ * written.  Event slots 8 and 9 bracket the kernels.                                   */
+int nmc_loo(nmc_ctx* ctx, int row_begin, int n_rows, int n_valid, int obs_batch,
+            double* elpd_i, double* lppd_i, double* k_i, int32_t* n_tail_i,
+            int64_t* nonfinite_i);
+/* The same sort and fit over a host array ll[rows][n_obs][C] in the store's layout (all of
+ * its rows), copied to `device`; needs no context.                                     */
+int nmc_psis_of(int device, const double* ll, int rows, int64_t n_obs, int C, int n_valid,
+                int obs_batch, double* elpd_i, double* lppd_i, double* k_i, int32_t* n_tail_i,
+                int64_t* nonfinite_i);
 
 /* Timing on the context's stream (hipEvents). */
 int nmc_event_record(nmc_ctx* ctx, int slot);                 /* slot 0..15 */

@@ -273,7 +273,8 @@ enum {
   NMC_OP_OBS_LL_ROWS = 4,  // sample rows [i0, i1), chains [c0, c0 + nc) -> out = [nc][i1 - i0][n_obs]
   NMC_OP_CAPACITY = 5,     // result = resident step-kernel workgroups on the device
   NMC_OP_RES_OK = 6,       // result = 1: the run mode has a resident instance, grid co-resident
-  NMC_OP_WAIC = 7          // sample rows [i0, i1), chains < nc valid -> out = [CB][5][n_obs] (waic.h)
+  NMC_OP_WAIC = 7,         // sample rows [i0, i1), chains < nc valid -> out = [CB][5][n_obs] (waic.h)
+  NMC_OP_LOO_LL = 8        // sample rows [i0, i1), observations [o0, o0 + nb) -> out = [i1 - i0][nb][C]
 };
 struct NmcCall {
   int op = 0;
@@ -281,6 +282,8 @@ struct NmcCall {
   int res = 0;             // NMC_OP_RUN: the resident instance (Dev.rcmd set)
   int c0 = 0, nc = 0;      // NMC_OP_OBS_LL_ROWS: chains [c0, c0 + nc) (nc = 0: every chain)
                            // NMC_OP_WAIC: nc = the valid chains (the others are padding)
+  int64_t o0 = 0;          // NMC_OP_LOO_LL: the batch's first observation
+  int nb = 0;              //                and its observations
   const double* in = nullptr;
   double* out = nullptr;
   double* aux = nullptr;   // op-specific device scratch

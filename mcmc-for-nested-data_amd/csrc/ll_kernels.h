@@ -121,6 +121,47 @@ nmc_k_obs_ll_rows(Dev d, Fam fam, const int* __restrict__ gidx, int64_t n_obs, i
   out[((size_t)blockIdx.y * nrows + r) * n_obs + i] = fam.obs_ll(reg, d.obs + i * Fam::NFIELDS);
 }
 
+// The same values in the sample store's layout, for the column sort of sortcol.h (PSIS-LOO,
+// psis.h): observations [o0, o0 + B) at rows [row0, row0 + nrows) ->
+// out[r][o - o0][C], the chain fastest.  Grid (ceil(B / (4 NMC_LOO_OT)), CB, min(nrows, 65535)),
+// 256 threads: lane = chain of chain block blockIdx.y, every load of theta and every store one
+// coalesced run of the wave; wave w of workgroup bx walks the NMC_LOO_OT consecutive
+// observations from o0 + (4 bx + w) NMC_LOO_OT on and prepares again only where the group
+// changes (wave-uniform).  theta's column arithmetic, prepare and obs_ll are
+// nmc_k_obs_ll_rows' own: every value has its bits.
+enum { NMC_LOO_OT = 8 };
+template <class Fam>
+__global__ void __launch_bounds__(256)
+nmc_k_loo_ll(Dev d, Fam fam, const int* __restrict__ gidx, int pc, int row0, int nrows,
+             int64_t o0, int B, double* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int c = (int)blockIdx.y * 64 + lane;
+  const int cc = c < d.C ? c : d.C - 1;   // (a padding lane reads the last chain, stores nothing)
+  const int b0 = ((int)blockIdx.x * 4 + w) * NMC_LOO_OT;
+  if (b0 >= B) return;
+  const int b1 = b0 + NMC_LOO_OT < B ? b0 + NMC_LOO_OT : B;
+  for (int r = blockIdx.z; r < nrows; r += gridDim.z) {
+    const double* row = d.samples + (size_t)(row0 + r) * d.cols * d.C + cc;
+    int gp = -1;
+    typename Fam::Reg reg;
+    for (int b = b0; b < b1; ++b) {
+      const int64_t i = o0 + b;
+      const int g = gidx[i];
+      if (g != gp) {
+        double th[Fam::MAXP];
+#pragma unroll
+        for (int q = 0; q < Fam::MAXP; ++q)
+          th[q] = q < d.P ? row[((size_t)q * (d.G + pc) + pc + g) * d.C] : 0.0;
+        reg = fam.prepare(th);
+        gp = g;
+      }
+      const double v = fam.obs_ll(reg, d.obs + i * Fam::NFIELDS);
+      if (c < d.C) out[((size_t)r * B + b) * d.C + c] = v;
+    }
+  }
+}
+
 // Per-observation LL at the values in `value` [P][G][C] -> out [C][n_obs].
 template <class Fam>
 __global__ void __launch_bounds__(64)

@@ -27,6 +27,7 @@
 #include "kernels_misc.h"
 #include "conv.h"          // nmc_k_conv: convergence partials over the sample store
 #include "sortcol.h"       // nmc_k_sort_*: the columns' sort and order statistics
+#include "psis.h"          // nmc_k_psis: PSIS-LOO over a sorted log-likelihood column
 
 #define NMC_VERSION "nestmc 0.2.0 (gfx950)"
 
@@ -1738,13 +1739,33 @@ static int summary_check(int rows, int C, int cols, int row_begin, int n_rows, i
   return 0;
 }
 
+// The sort of columns [c0, c0 + k) of a store samples[row][cols][C] over rows [row_begin, ...)
+// and chains [0, n_valid), N values each: the tile launch and the merge passes (sortcol.h),
+// shared by the summary and PSIS-LOO.  The sorted keys end in buf[*cur] as [k][N];
+// nonfinite[c0 + j] counts column j's values that are not finite.
+static hipError_t sort_columns(hipStream_t st, const double* samples, int C, int cols,
+                               int row_begin, int n_valid, int64_t N, int c0, int k,
+                               uint64_t* const buf[2], unsigned long long* nonfinite, int* cur) {
+  const int64_t tiles = (N + NMC_SORT_TILE - 1) / NMC_SORT_TILE;
+  const dim3 grid((unsigned)tiles, (unsigned)k);
+  hipLaunchKernelGGL(nmc_k_sort_tiles, grid, dim3(NMC_SORT_THREADS), 0, st, samples, C, cols,
+                     row_begin, n_valid, N, c0, buf[0], nonfinite);
+  hipError_t e = hipGetLastError();
+  *cur = 0;
+  for (int64_t L = NMC_SORT_TILE; L < N && e == hipSuccess; L *= 2, *cur ^= 1) {
+    hipLaunchKernelGGL(nmc_k_sort_merge, grid, dim3(NMC_SORT_THREADS), 0, st, buf[*cur],
+                       buf[*cur ^ 1], N, L);
+    e = hipGetLastError();
+  }
+  return e;
+}
+
 // x: the context whose event slots 10 / 11 bracket the kernels, or NULL.
 static int summary_run(nmc_ctx* x, hipStream_t st, const double* samples, int C, int cols,
                        int row_begin, int n_rows, int n_valid, int64_t gap, const int64_t* ranks,
                        int n_ranks, int col_batch, double* at_ranks, double* hdi,
                        int64_t* hdi_at, int64_t* nonfinite, double* sorted) {
   const int64_t N = (int64_t)n_rows * n_valid;
-  const int64_t tiles = (N + NMC_SORT_TILE - 1) / NMC_SORT_TILE;
   const size_t budget = (size_t)1 << 30;
   int64_t kb = col_batch > 0 ? col_batch : (int64_t)(budget / ((size_t)N * 16));
   kb = std::max<int64_t>(1, std::min<int64_t>({kb, (int64_t)cols, (int64_t)65535}));
@@ -1773,16 +1794,8 @@ static int summary_run(nmc_ctx* x, hipStream_t st, const double* samples, int C,
   if (e == hipSuccess && x) rc = nmc_event_record(x, 10);
   for (int c0 = 0; c0 < cols && e == hipSuccess && !rc; c0 += (int)kb) {
     const int k = (int)std::min<int64_t>(kb, cols - c0);
-    const dim3 grid((unsigned)tiles, (unsigned)k);
-    hipLaunchKernelGGL(nmc_k_sort_tiles, grid, dim3(NMC_SORT_THREADS), 0, st, samples, C, cols,
-                       row_begin, n_valid, N, c0, buf[0], d_bad);
-    e = hipGetLastError();
     int cur = 0;
-    for (int64_t L = NMC_SORT_TILE; L < N && e == hipSuccess; L *= 2, cur ^= 1) {
-      hipLaunchKernelGGL(nmc_k_sort_merge, grid, dim3(NMC_SORT_THREADS), 0, st, buf[cur],
-                         buf[cur ^ 1], N, L);
-      e = hipGetLastError();
-    }
+    e = sort_columns(st, samples, C, cols, row_begin, n_valid, N, c0, k, buf, d_bad, &cur);
     if (e == hipSuccess) {
       hipLaunchKernelGGL(nmc_k_sort_scan, dim3((unsigned)k), dim3(NMC_SORT_THREADS), 0, st,
                          buf[cur], N, gap, d_ranks, n_ranks, c0, d_bad, d_at, d_hdi, d_hat);
@@ -1844,6 +1857,169 @@ int nmc_summary_of(int device, const double* xs, int rows, int cols, int C, int 
                ? summary_run(nullptr, st, dx, C, cols, row_begin, n_rows, n_valid, gap, ranks,
                              n_ranks, col_batch, at_ranks, hdi, hdi_at, nonfinite, sorted)
                : fail(-2, std::string("summary_of: ") + hipGetErrorString(e));
+  hipStreamSynchronize(st);
+  hipFree(dx);
+  hipStreamDestroy(st);
+  return rc;
+}
+
+// PSIS-LOO (psis.h; nestmc/loo.py has the definitions; include/nestmc.h) -- no reference
+// counterpart.  The observations go in batches: the batch's log-likelihoods in store layout
+// [n_rows][batch][C] (stage: nmc_k_loo_ll into a buffer of the batch, or the caller's array
+// as it lies), sort_columns over them, nmc_k_psis on every sorted column.
+static int psis_check(int rows, int C, int64_t n_obs, int row_begin, int n_rows, int n_valid,
+                      int obs_batch, int64_t* Mout) {
+  if (n_obs < 1) return fail(-1, "loo: no observations");
+  if (n_rows < 1 || row_begin < 0 || row_begin > rows - n_rows)
+    return fail(-1, "loo: row range out of bounds");
+  if (n_valid < 1 || n_valid > C) return fail(-1, "n_valid must be in 1..n_chains");
+  if (obs_batch < 0) return fail(-1, "loo: obs_batch must not be negative");
+  const int64_t S = (int64_t)n_rows * n_valid;
+  if (S < 2) return fail(-1, "loo: an observation needs at least two samples");
+  if (S >= ((int64_t)1 << 31)) return fail(-1, "loo: 2^31 or more samples per observation");
+  const int64_t M = nmc_psis_m(S);
+  if (M > NMC_PSIS_MAXTAIL) return fail(-1, "loo: a tail of more than 8191 values");
+  if (M < 1 || M >= S) return fail(-1, "loo: no cutoff position");   // (never for S >= 2)
+  *Mout = M;
+  return 0;
+}
+
+// The observations of a batch such that the LL of the batch (ll_bytes_per_obs each; 0: the
+// caller's array) and the two key buffers fit 1 GiB, or obs_batch of them.
+static int64_t psis_batch(int64_t n_obs, int64_t S, size_t ll_bytes_per_obs, int obs_batch) {
+  const size_t budget = (size_t)1 << 30;
+  int64_t kb = obs_batch > 0 ? obs_batch : (int64_t)(budget / ((size_t)S * 16 + ll_bytes_per_obs));
+  return std::max<int64_t>(1, std::min<int64_t>({kb, n_obs, (int64_t)65535}));
+}
+
+// stage(o0, k, &samples, &cols, &col0): the store that holds observations [o0, o0 + k) as its
+// columns [col0, col0 + k) of cols (rows [row_begin, ...) of it are the window).
+// x: the context whose event slots 8 / 9 bracket the kernels, or NULL.
+extern "C++" {
+template <class Stage>
+static int psis_run(nmc_ctx* x, hipStream_t st, int C, int row_begin, int n_rows, int n_valid,
+                    int64_t n_obs, int64_t kb, int64_t M, Stage&& stage, double* elpd_i,
+                    double* lppd_i, double* k_i, int32_t* n_tail_i, int64_t* nonfinite_i) {
+  const int64_t S = (int64_t)n_rows * n_valid;
+  uint64_t* buf[2] = {nullptr, nullptr};
+  double* d_out = nullptr;   // [3][n_obs]: elpd, lppd, k
+  int* d_nt = nullptr;
+  int64_t* d_nf = nullptr;
+  unsigned long long* d_bad = nullptr;
+  const size_t lds = (size_t)M * 8;
+  hipError_t e = hipSuccess;
+  if (lds > 60 * 1024)   // (with the kernel's static 3.3 KiB: past the 64 KiB every launch may have)
+    e = hipFuncSetAttribute((const void*)nmc_k_psis, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)lds);
+  if (e == hipSuccess) e = hipMalloc(&buf[0], (size_t)kb * S * 8);
+  if (e == hipSuccess) e = hipMalloc(&buf[1], (size_t)kb * S * 8);
+  if (e == hipSuccess) e = hipMalloc(&d_out, (size_t)n_obs * 24);
+  if (e == hipSuccess) e = hipMalloc(&d_nt, (size_t)n_obs * 4);
+  if (e == hipSuccess) e = hipMalloc(&d_nf, (size_t)n_obs * 8);
+  if (e == hipSuccess) e = hipMalloc(&d_bad, (size_t)n_obs * 8);
+  if (e == hipSuccess) e = hipMemsetAsync(d_bad, 0, (size_t)n_obs * 8, st);
+  int rc = 0;
+  if (e == hipSuccess && x) rc = nmc_event_record(x, 8);
+  for (int64_t o0 = 0; o0 < n_obs && e == hipSuccess && !rc; o0 += kb) {
+    const int k = (int)std::min<int64_t>(kb, n_obs - o0);
+    const double* samples = nullptr;
+    int cols = 0, col0 = 0;
+    rc = stage(o0, k, &samples, &cols, &col0);
+    if (rc) break;
+    int cur = 0;
+    // (nmc_k_sort_tiles counts into nonfinite[col0 + j]: observation o0 + j's entry)
+    e = sort_columns(st, samples, C, cols, row_begin, n_valid, S, col0, k, buf,
+                     d_bad + o0 - col0, &cur);
+    if (e == hipSuccess) {
+      hipLaunchKernelGGL(nmc_k_psis, dim3((unsigned)k), dim3(NMC_PSIS_THREADS), lds, st,
+                         (const uint64_t*)buf[cur], S, (int)M,
+                         (const unsigned long long*)(d_bad + o0), d_out + o0,
+                         d_out + n_obs + o0, d_out + 2 * n_obs + o0, d_nt + o0, d_nf + o0);
+      e = hipGetLastError();
+    }
+  }
+  if (e == hipSuccess && !rc && x) rc = nmc_event_record(x, 9);
+  const size_t nb = (size_t)n_obs * 8;
+  if (e == hipSuccess && !rc) e = hipMemcpyAsync(elpd_i, d_out, nb, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess && !rc)
+    e = hipMemcpyAsync(lppd_i, d_out + n_obs, nb, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess && !rc)
+    e = hipMemcpyAsync(k_i, d_out + 2 * n_obs, nb, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess && !rc)
+    e = hipMemcpyAsync(n_tail_i, d_nt, (size_t)n_obs * 4, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess && !rc) e = hipMemcpyAsync(nonfinite_i, d_nf, nb, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess && !rc) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) rc = fail(-2, std::string("loo: ") + hipGetErrorString(e));
+  hipStreamSynchronize(st);
+  hipFree(buf[0]); hipFree(buf[1]); hipFree(d_out); hipFree(d_nt); hipFree(d_nf); hipFree(d_bad);
+  return rc;
+}
+}  // extern "C++"
+
+int nmc_loo(nmc_ctx* x, int row_begin, int n_rows, int n_valid, int obs_batch, double* elpd_i,
+            double* lppd_i, double* k_i, int32_t* n_tail_i, int64_t* nonfinite_i) {
+  RES_PARK(x);
+  hipSetDevice(x->device);
+  int64_t M = 0;
+  if (int rc = psis_check(x->d.n_rows, x->C, x->n_obs, row_begin, n_rows, n_valid, obs_batch, &M))
+    return rc;
+  HIPCHK(hipStreamSynchronize(x->stream));
+  if (int rc = check_timeout(x)) return rc;
+  if (int rc = ensure_gidx(x)) return rc;
+  const int64_t S = (int64_t)n_rows * n_valid;
+  const size_t per_obs = (size_t)n_rows * x->C * 8;
+  const int64_t kb = psis_batch(x->n_obs, S, per_obs, obs_batch);
+  double* ll = nullptr;
+  HIPCHK(hipMalloc(&ll, (size_t)kb * per_obs));
+  const int rc = psis_run(
+      x, x->stream, x->C, 0, n_rows, n_valid, x->n_obs, kb, M,
+      [&](int64_t o0, int k, const double** samples, int* cols, int* col0) {
+        NmcCall c;
+        c.op = NMC_OP_LOO_LL;
+        c.i0 = row_begin;
+        c.i1 = row_begin + n_rows;
+        c.o0 = o0;
+        c.nb = k;
+        c.out = ll;
+        *samples = ll;   // [n_rows][k][C]: the batch is the whole store, its window row 0 on
+        *cols = k;
+        *col0 = 0;
+        return nmc_call_family(x, c);
+      },
+      elpd_i, lppd_i, k_i, n_tail_i, nonfinite_i);
+  hipFree(ll);
+  return rc;
+}
+
+int nmc_psis_of(int device, const double* ll, int rows, int64_t n_obs, int C, int n_valid,
+                int obs_batch, double* elpd_i, double* lppd_i, double* k_i, int32_t* n_tail_i,
+                int64_t* nonfinite_i) {
+  if (rows < 1 || C < 1) return fail(-1, "psis_of: need rows >= 1 and C >= 1");
+  if (n_obs > 0x7fffffff) return fail(-1, "psis_of: too many observations");
+  int64_t M = 0;
+  if (int rc = psis_check(rows, C, n_obs, 0, rows, n_valid, obs_batch, &M)) return rc;
+  HIPCHK(hipSetDevice(device));
+  hipStream_t st;
+  HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+  double* dx = nullptr;
+  const size_t nx = (size_t)rows * n_obs * C;
+  hipError_t e = hipMalloc(&dx, nx * 8);
+  if (e == hipSuccess) e = hipMemcpyAsync(dx, ll, nx * 8, hipMemcpyHostToDevice, st);
+  int rc = 0;
+  if (e == hipSuccess) {
+    const int64_t kb = psis_batch(n_obs, (int64_t)rows * n_valid, 0, obs_batch);
+    rc = psis_run(
+        nullptr, st, C, 0, rows, n_valid, n_obs, kb, M,
+        [&](int64_t o0, int, const double** samples, int* cols, int* col0) {
+          *samples = dx;
+          *cols = (int)n_obs;
+          *col0 = (int)o0;
+          return 0;
+        },
+        elpd_i, lppd_i, k_i, n_tail_i, nonfinite_i);
+  } else {
+    rc = fail(-2, std::string("psis_of: ") + hipGetErrorString(e));
+  }
   hipStreamSynchronize(st);
   hipFree(dx);
   hipStreamDestroy(st);

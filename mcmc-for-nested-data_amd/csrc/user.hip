@@ -24,9 +24,10 @@ namespace {
 
 // kernel table entries, in name-expression order
 // (nmc_k_run: mode m (0..4) with rows in LDS at UK_RUN0 + m, rows staged at UK_RUN0 + 5 + m;
-// the half layout at UK_HALF; WAIC's reduction, waic.h, at UK_WAIC)
+// the half layout at UK_HALF; WAIC's reduction, waic.h, at UK_WAIC; the LL in store layout of
+// PSIS-LOO, ll_kernels.h, at UK_LOO_LL)
 enum { UK_RUN0 = 0, UK_NRUN = 5, UK_GROUP_LL = 10, UK_OBS_LL_ROWS = 11, UK_OBS_LL = 12,
-       UK_GROUP_LL_RL = 13, UK_GROUP_FIN = 14, UK_HALF = 15, UK_WAIC = 16, UK_N = 17 };
+       UK_GROUP_LL_RL = 13, UK_GROUP_FIN = 14, UK_HALF = 15, UK_WAIC = 16, UK_LOO_LL = 17, UK_N = 18 };
 const char* const kNames[UK_N] = {
     "nmc_k_run<FamUser, 0, true>", "nmc_k_run<FamUser, 1, true>", "nmc_k_run<FamUser, 2, true>",
     "nmc_k_run<FamUser, 3, true>", "nmc_k_run<FamUser, 4, true>",
@@ -35,7 +36,7 @@ const char* const kNames[UK_N] = {
     "nmc_k_run<FamUser, 4, false>",
     "nmc_k_group_part<FamUser, false>", "nmc_k_obs_ll_rows<FamUser>",
     "nmc_k_obs_ll<FamUser>", "nmc_k_group_part<FamUser, true>", "nmc_k_group_fin<FamUser>",
-    "nmc_k_run<FamUser, 6, true>", "nmc_k_waic<FamUser>"};
+    "nmc_k_run<FamUser, 6, true>", "nmc_k_waic<FamUser>", "nmc_k_loo_ll<FamUser>"};
 int run_index(const nmc_ctx* x, int mode) {
   if (mode == NMC_MODE_HALF) return UK_HALF;
   return UK_RUN0 + mode + (x->d.rows_lds ? 0 : UK_NRUN);
@@ -279,6 +280,21 @@ int nmc_call_user(nmc_ctx* x, NmcCall& c) {
       if (int rc = user_fn(x, UK_WAIC, &f)) return rc;
       return launch(x, f, dim3((unsigned)((x->n_wtiles + 3) / 4), (unsigned)d0.CB), dim3(256),
                     0, args);
+    }
+    case NMC_OP_LOO_LL: {
+      int nrows = c.i1 - c.i0, nb = c.nb;
+      if (nrows <= 0 || nb <= 0) return 0;
+      Dev dd = d0;
+      const int* gidx = (const int*)x->gidx;
+      int pc = x->pooling == NMC_POOL_PARTIAL ? 2 : 0, row0 = c.i0;
+      int64_t o0 = c.o0;
+      double* out = c.out;
+      void* args[] = {&dd, &fam, (void*)&gidx, &pc, &row0, &nrows, &o0, &nb, &out};
+      if (int rc = user_fn(x, UK_LOO_LL, &f)) return rc;
+      return launch(x, f,
+                    dim3((unsigned)((nb + 4 * NMC_LOO_OT - 1) / (4 * NMC_LOO_OT)),
+                         (unsigned)d0.CB, (unsigned)std::min(nrows, 65535)),
+                    dim3(256), 0, args);
     }
     case NMC_OP_OBS_LL: {
       Dev dd = d0;

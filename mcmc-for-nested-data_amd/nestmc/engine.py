@@ -243,6 +243,40 @@ class Engine:
         parts = self.waic_partials(row_begin, n_rows, n_valid)
         return _waic.finish(_waic.merge(list(parts)), self.off)
 
+    def loo_raw(self, row_begin=0, n_rows=None, n_valid=None, obs_batch=0):
+        """PSIS-LOO's per-observation results over recorded rows [row_begin, row_begin +
+        n_rows) and local chains [0, n_valid), computed on the device from the sample store
+        (nmc_loo; nestmc.loo): a dict of elpd, lppd, k [n_obs], n_tail [n_obs] (int32) and
+        nonfinite [n_obs] (an observation with NaN or infinite log-likelihoods has NaN
+        results).  obs_batch: the observations sorted at a time (0: what fits the 1 GiB of
+        temporary buffers); the results do not depend on it."""
+        if n_rows is None:
+            n_rows = self.n_rows - row_begin
+        if n_valid is None:
+            n_valid = self.C
+        n = int(self.off[-1])
+        elpd, lppd, k = numpy.empty(n), numpy.empty(n), numpy.empty(n)
+        nt = numpy.empty(n, dtype=numpy.int32)
+        bad = numpy.empty(n, dtype=numpy.int64)
+        check(self.lib.nmc_loo(self.h, int(row_begin), int(n_rows), int(n_valid), int(obs_batch),
+                               dptr(elpd), dptr(lppd), dptr(k),
+                               nt.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                               bad.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
+        return dict(elpd=elpd, lppd=lppd, k=k, n_tail=nt, nonfinite=bad,
+                    n_samples=int(n_rows) * int(n_valid))
+
+    def loo(self, row_begin=0, n_rows=None, n_valid=None, obs_batch=0):
+        """The LooResult (nestmc.loo) of this engine's chains over the given rows.  A
+        log-likelihood term that is not finite is an error."""
+        from . import loo as _loo
+        raw = self.loo_raw(row_begin, n_rows, n_valid, obs_batch)
+        self.loo_nonfinite = int(raw["nonfinite"].sum())
+        if self.loo_nonfinite:
+            raise _lib.NestmcError("PSIS-LOO: %d per-observation log-likelihood terms were not "
+                                   "finite" % self.loo_nonfinite)
+        return _loo.LooResult(raw["elpd"], raw["lppd"], raw["k"], raw["n_tail"],
+                              raw["n_samples"], self.off)
+
     def conv_partials(self, row_begin=0, n_rows=None, n_valid=None):
         """The convergence diagnostic's partial sums over recorded rows [row_begin, row_begin +
         n_rows) (n_rows even, two halves of n = n_rows / 2 >= 2 rows) and local chains

@@ -25,6 +25,7 @@ from . import _lib
 from . import output
 from . import convergence as _conv
 from . import summary as _summary
+from . import loo as _loo
 from . import waic as _waic
 from .engine import Engine
 from .families import is_family
@@ -64,7 +65,8 @@ def sample_posterior(nChains, nIter, nSamples, parameterName, nGroups, nResponse
                      nProcesses=1, displayProgress=True, loggingLevel="info", *,
                      seed=0, devices=None, rng="philox", chains=None, return_samples=False,
                      write_files=True, replay=None, process_per_device=False, _rank=None,
-                     computeWaic=False, computeDiagnostics=False, computeSummary=False):
+                     computeWaic=False, computeDiagnostics=False, computeSummary=False,
+                     computeLoo=False):
     """Drop-in for posteriorSampling.samplePosterior (same positional/keyword API).
 
     Extra keyword-only options (all optional):
@@ -106,6 +108,14 @@ def sample_posterior(nChains, nIter, nSamples, parameterName, nGroups, nResponse
                  sorted columns on the host -- as many bytes as the sample gather those paths
                  already do.  Fewer than two values per column raise ValueError before
                  sampling starts
+      computeLoo  after the loop, compute PSIS-LOO on the GPU from the device sample store
+                 (nestmc.loo): elpd_loo with its pointwise terms and the Pareto k of every
+                 observation, which says which terms not to trust: outputDirectory/loo.csv
+                 and loo_pointwise.csv, "loo" (a nestmc.loo.LooResult) in the returned dict,
+                 and one warning line in the log when some k exceed the threshold.  One
+                 engine only: with several devices, chains= shards or process_per_device it
+                 raises NotImplementedError before sampling starts (DESIGN section 10 has the
+                 protocol that would lift this)
     nProcesses sizes the host threads used for chain initialisation and CSV writing.
     """
     start_time = datetime.datetime.now()
@@ -123,6 +133,11 @@ def sample_posterior(nChains, nIter, nSamples, parameterName, nGroups, nResponse
             "(INTEGRATION.md, 'Porting a likelihood callable').")
     if pooling not in ("partial", "none", "complete"):
         raise Exception("Invalid pooling: ", pooling)
+    if computeLoo and ((devices is not None and len(list(devices)) > 1) or chains is not None
+                       or process_per_device or _rank is not None):
+        raise NotImplementedError(
+            "computeLoo needs every chain in one engine: several devices, chains= shards and "
+            "process_per_device are not supported yet")
     names = tuple(parameterName)
     if len(names) != logLikelihoodFunction.n_params:
         raise ValueError("parameterName has %d names, the likelihood family has %d parameters"
@@ -163,6 +178,8 @@ def sample_posterior(nChains, nIter, nSamples, parameterName, nGroups, nResponse
         if n_val < 2:
             raise ValueError("computeSummary needs at least two values per column: the "
                              "recorded rows of all chains give %d" % n_val)
+    if computeLoo and len(record_iterations(nIter, burn, thin)) * nChains < 2:
+        raise ValueError("computeLoo needs at least two samples")
     sizes = _sizes(nGroups, nResponsesPerGroup, pooling)
     G = len(sizes)
     priors = None
@@ -278,7 +295,7 @@ def sample_posterior(nChains, nIter, nSamples, parameterName, nGroups, nResponse
                             logger, chain_logs, start_time, rank_info,
                             compute_waic=bool(computeWaic), waic_dir=outputDirectory,
                             n_real=nChains, compute_conv=bool(computeDiagnostics),
-                            compute_summary=bool(computeSummary))
+                            compute_summary=bool(computeSummary), compute_loo=bool(computeLoo))
     finally:
         for eng, _, _ in engines:
             eng.close()
@@ -417,7 +434,7 @@ def _summary_of(engines, rank_info, n_real, header):
 def _sample_loop(engines, nIter, burn, thin, names, G, partial, saveLogLikelihood, write_files,
                  sample_dir, threads, displayProgress, return_samples, logger, chain_logs,
                  start_time, rank_info=None, compute_waic=False, waic_dir=None,
-                 n_real=None, compute_conv=False, compute_summary=False):
+                 n_real=None, compute_conv=False, compute_summary=False, compute_loo=False):
     """The device loop, the per-observation LL rows and the sample files of
     sample_posterior (the caller closes the engines whatever happens here).  rank_info: a
     rank of process_per_device -- this rank writes its chains' logLikelihood files, rank 0
@@ -459,6 +476,18 @@ def _sample_loop(engines, nIter, burn, thin, names, G, partial, saveLogLikelihoo
         waic_result = _waic_of(engines, rank_info, n_real)
         if waic_result is not None and write_files:
             _waic.write_csvs(waic_result, waic_dir)
+
+    loo_result = None
+    if compute_loo:   # (one engine, no padding chains: sample_posterior checked)
+        loo_result = engines[0][0].loo()
+        if write_files:
+            _loo.write_csvs(loo_result, waic_dir)
+        warn = loo_result.warning()
+        if warn:
+            if logger:
+                logger.warning(warn)
+            if displayProgress:
+                output.print_progress(warn)
 
     header = output.header_names(names, G, partial)
     conv_result = None
@@ -504,6 +533,8 @@ def _sample_loop(engines, nIter, burn, thin, names, G, partial, saveLogLikelihoo
                "loop_seconds": loop_seconds}
         if waic_result is not None:
             res["waic"] = waic_result
+        if loo_result is not None:
+            res["loo"] = loo_result
         if conv_result is not None:
             res["convergence"] = conv_result
         if summary_result is not None:

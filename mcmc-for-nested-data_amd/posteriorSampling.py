@@ -25,7 +25,7 @@ def samplePosterior(nChains, nIter, nSamples,
                     startWithMLE=False, startingPointValueRange=None,
                     nProcesses=1, displayProgress=True, loggingLevel="info",
                     computeWaic=False, computeDiagnostics=False, computeSummary=False,
-                    **gpu_options):
+                    computeLoo=False, **gpu_options):
     """Sample the posterior of a nested model; samples go to outputDirectory/sample/.
 
     Arguments mirror the reference (posteriorSampling.py:28-145).  Keyword-only
@@ -36,7 +36,9 @@ def samplePosterior(nChains, nIter, nSamples,
     size of every column on the GPU from the device sample store (convergence.csv;
     nestmc.convergence) -- an even number of recorded rows is needed.  computeSummary=True
     also sorts every column of the store on the GPU for its median, 95 % HDI, minimum and
-    maximum (summary.csv; nestmc.summary).  Returns None like the reference unless
+    maximum (summary.csv; nestmc.summary).  computeLoo=True also computes PSIS-LOO with the
+    Pareto k diagnostic of every observation on the GPU (loo.csv, loo_pointwise.csv;
+    nestmc.loo) -- one engine only.  Returns None like the reference unless
     return_samples=True.
     """
     return sample_posterior(nChains, nIter, nSamples, parameterName, nGroups,
@@ -47,5 +49,5 @@ def samplePosterior(nChains, nIter, nSamples,
                             nProcesses=nProcesses, displayProgress=displayProgress,
                             loggingLevel=loggingLevel, computeWaic=computeWaic,
                             computeDiagnostics=computeDiagnostics,
-                            computeSummary=computeSummary,
+                            computeSummary=computeSummary, computeLoo=computeLoo,
                             **gpu_options)
