@@ -276,6 +276,39 @@ int nmc_loo(nmc_ctx* ctx, int row_begin, int n_rows, int n_valid, int obs_batch,
 int nmc_psis_of(int device, const double* ll, int rows, int64_t n_obs, int C, int n_valid,
                 int obs_batch, double* elpd_i, double* lppd_i, double* k_i, int32_t* n_tail_i,
                 int64_t* nonfinite_i);
+/* The rank-normalised convergence diagnostics' partial sums (Vehtari, Gelman, Simpson,
+ * Carpenter, Buerkner 2021; the definitions are nestmc/rankdiag.py's docstring) over recorded
+ * rows [row_begin, row_begin + n_rows) and local chains [0, n_valid), on the device from the
+ * sample store.  A column's N = n_rows * n_valid values are sorted (the kernels of
+ * nmc_summary); every value x becomes four derived values, in this order (csrc/rankz.h):
+ *   z    the normal score of its average rank r: ndtri((r - 0.375) / (N + 0.25)), ties
+ *        numeric (-0.0 ties +0.0), 2 r = #{< x} + #{<= x} + 1
+ *   zf   the same of zeta = |x - med| among the column's zeta, med = (s[N/2-1] + s[N/2]) / 2.0
+ *   I05  1.0 if #{< x} <= (N - 1) / 20, else 0.0          (x <= the lower 5 % order statistic)
+ *   I95  1.0 if #{< x} <= 19 (N - 1) / 20, else 0.0
+ * written in the store's layout, and each derived column gets exactly nmc_conv_partials' sums
+ * (the same kernel): vg[4][CB][cols][n], mean[4][cols][2][C], m2[4][cols][2][C], n = n_rows / 2.
+ * nonfinite[col]: the column's values that are NaN or +-inf; such a column's derived values
+ * are all NaN.  nestmc/rankdiag.py finishes.  Columns go in batches whose temporary buffers
+ * (two key buffers and the derived values, 16 N + 32 n_rows C bytes a column, allocated and
+ * freed by the call) fit 1 GiB; col_batch > 0 sets the columns per batch, and no bit depends
+ * on it.  n_rows even and >= 4, the rows inside the schedule's, 1 <= n_valid <= C, N < 2^31,
+ * col_batch >= 0, else -1 and nothing is written.  Event slots 6 and 7 bracket the kernels
+ * (with several batches also the earlier batches' copies).                              */
+int nmc_rank_partials(nmc_ctx* ctx, int row_begin, int n_rows, int n_valid, int col_batch,
+                      double* vg, double* mean, double* m2, int64_t* nonfinite);
+/* The same over a host array x[rows][cols][C] in the store's layout (all of its rows), copied
+ * to `device`; needs no context.  Three more outputs, each may be NULL:
+ *   derived[4][rows][cols][C]     the derived values (z, zf, I05, I95); chains >= n_valid +0.0
+ *   twice_rank[2][rows][cols][C]  #{<} + #{<=} + 1 of x among the x and of zeta among the
+ *                                 zeta; 0 for chains >= n_valid and for a column counted in
+ *                                 nonfinite
+ *   zeta[rows][cols][C]           |x - med| as pass 1 wrote it (pass 2 replaces it by zf);
+ *                                 chains >= n_valid +0.0, NaN for a column counted in nonfinite */
+int nmc_rank_partials_of(int device, const double* x, int rows, int cols, int C, int n_valid,
+                         int col_batch, double* vg, double* mean, double* m2,
+                         int64_t* nonfinite, double* derived, int64_t* twice_rank,
+                         double* zeta);
 
 /* Timing on the context's stream (hipEvents). */
 int nmc_event_record(nmc_ctx* ctx, int slot);                 /* slot 0..15 */

@@ -28,6 +28,7 @@
 #include "conv.h"          // nmc_k_conv: convergence partials over the sample store
 #include "sortcol.h"       // nmc_k_sort_*: the columns' sort and order statistics
 #include "psis.h"          // nmc_k_psis: PSIS-LOO over a sorted log-likelihood column
+#include "rankz.h"         // nmc_k_rank_transform: values to their ranks' normal scores
 
 #define NMC_VERSION "nestmc 0.2.0 (gfx950)"
 
@@ -1857,6 +1858,156 @@ int nmc_summary_of(int device, const double* xs, int rows, int cols, int C, int 
                ? summary_run(nullptr, st, dx, C, cols, row_begin, n_rows, n_valid, gap, ranks,
                              n_ranks, col_batch, at_ranks, hdi, hdi_at, nonfinite, sorted)
                : fail(-2, std::string("summary_of: ") + hipGetErrorString(e));
+  hipStreamSynchronize(st);
+  hipFree(dx);
+  hipStreamDestroy(st);
+  return rc;
+}
+
+// Rank-normalised R-hat, bulk- and tail-ESS (rankz.h; nestmc/rankdiag.py has the definitions;
+// include/nestmc.h) -- no reference counterpart.  Per batch of k columns, on one stream:
+// sort_columns on the store, transform pass 1 into D[2n][4 k][C], sort_columns on D's zeta
+// range, transform pass 2, nmc_k_conv on D, the partials copied out per quantity.
+static int rank_check(int rows, int C, int cols, int row_begin, int n_rows, int n_valid,
+                      int col_batch) {
+  if (cols < 1) return fail(-1, "rank_partials: no columns");
+  if (n_rows < 4 || (n_rows & 1))
+    return fail(-1, "rank_partials: n_rows must be even and at least 4 (two halves of n >= 2)");
+  if (row_begin < 0 || row_begin > rows - n_rows)
+    return fail(-1, "rank_partials: row range out of bounds");
+  if (n_valid < 1 || n_valid > C) return fail(-1, "n_valid must be in 1..n_chains");
+  if (col_batch < 0) return fail(-1, "rank_partials: col_batch must not be negative");
+  if ((int64_t)n_rows * n_valid >= ((int64_t)1 << 31))
+    return fail(-1, "rank_partials: 2^31 or more values per column");
+  return 0;
+}
+
+// x: the context whose event slots 6 / 7 bracket the kernels, or NULL.
+static int rank_run(nmc_ctx* x, hipStream_t st, const double* samples, int C, int cols,
+                    int row_begin, int n_rows, int n_valid, int col_batch, double* vg,
+                    double* mean, double* m2, int64_t* nonfinite, double* derived,
+                    int64_t* twice_rank, double* zeta) {
+  const int64_t N = (int64_t)n_rows * n_valid;
+  const int n = n_rows / 2, nlb = (n - 1 + NMC_CONV_L - 1) / NMC_CONV_L, CB = (C + 63) / 64;
+  const size_t budget = (size_t)1 << 30;
+  const size_t per_col = (size_t)N * 16 + (size_t)4 * n_rows * C * 8;   // two key buffers and D
+  int64_t kb = col_batch > 0 ? col_batch : (int64_t)(budget / per_col);
+  // (the sorts' grid.y = k and nmc_k_conv's grid.x = (nlb + 1) * 4 k)
+  kb = std::max<int64_t>(1, std::min<int64_t>({kb, (int64_t)cols, (int64_t)16383,
+                                               (int64_t)(0x7fffffff / (4 * ((int64_t)nlb + 1)))}));
+  if (CB > 65535) return fail(-1, "rank_partials: too many chain blocks");
+  uint64_t* buf[2] = {nullptr, nullptr};
+  double *D = nullptr, *o = nullptr;
+  unsigned long long *d_bad = nullptr, *d_scratch = nullptr;
+  long long* d_tr = nullptr;
+  const size_t nd = (size_t)n_rows * 4 * kb * C;                        // D
+  const size_t nv = (size_t)CB * 4 * kb * n, nm = (size_t)4 * kb * 2 * C;   // nmc_k_conv's outputs
+  const size_t ntr = (size_t)n_rows * cols * C;                         // one pass' twice_rank
+  hipError_t e = hipMalloc(&buf[0], (size_t)kb * N * 8);
+  if (e == hipSuccess) e = hipMalloc(&buf[1], (size_t)kb * N * 8);
+  if (e == hipSuccess) e = hipMalloc(&D, nd * 8);
+  if (e == hipSuccess) e = hipMalloc(&o, (nv + 2 * nm) * 8);
+  if (e == hipSuccess) e = hipMalloc(&d_bad, (size_t)cols * 8);
+  if (e == hipSuccess) e = hipMalloc(&d_scratch, (size_t)4 * kb * 8);
+  if (e == hipSuccess && twice_rank) e = hipMalloc(&d_tr, 2 * ntr * 8);
+  if (e == hipSuccess) e = hipMemsetAsync(d_bad, 0, (size_t)cols * 8, st);
+  if (e == hipSuccess) e = hipMemsetAsync(d_scratch, 0, (size_t)4 * kb * 8, st);
+  // the padding chains' lanes of D are never written (nor read by a kernel): +0.0 for the copy
+  if (e == hipSuccess && (derived || zeta) && n_valid < C) e = hipMemsetAsync(D, 0, nd * 8, st);
+  if (e == hipSuccess && d_tr) e = hipMemsetAsync(d_tr, 0, 2 * ntr * 8, st);
+  int rc = 0;
+  if (e == hipSuccess && x) rc = nmc_event_record(x, 6);
+  const dim3 blk(NMC_RANK_THREADS);
+  for (int c0 = 0; c0 < cols && e == hipSuccess && !rc; c0 += (int)kb) {
+    const int k = (int)std::min<int64_t>(kb, cols - c0);
+    const dim3 grid((unsigned)((N + NMC_RANK_TILE - 1) / NMC_RANK_TILE), (unsigned)k);
+    int cur = 0;
+    e = sort_columns(st, samples, C, cols, row_begin, n_valid, N, c0, k, buf, d_bad, &cur);
+    if (e == hipSuccess) {
+      hipLaunchKernelGGL(nmc_k_rank_transform<1>, grid, blk, 0, st, samples, C, cols, row_begin,
+                         c0, n_valid, N, (const uint64_t*)buf[cur], D, k,
+                         (const unsigned long long*)d_bad, c0, d_tr, cols, c0);
+      e = hipGetLastError();
+    }
+    // D is a store of 4 k columns whose window starts at its row 0; zeta: columns [k, 2 k)
+    if (e == hipSuccess && zeta)   // (before pass 2 overwrites it)
+      e = hipMemcpy2DAsync(zeta + (size_t)c0 * C, (size_t)cols * C * 8, D + (size_t)k * C,
+                           (size_t)4 * k * C * 8, (size_t)k * C * 8, n_rows,
+                           hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess)
+      e = sort_columns(st, D, C, 4 * k, 0, n_valid, N, k, k, buf, d_scratch, &cur);
+    if (e == hipSuccess) {
+      hipLaunchKernelGGL(nmc_k_rank_transform<2>, grid, blk, 0, st, (const double*)D, C, 4 * k, 0,
+                         k, n_valid, N, (const uint64_t*)buf[cur], D, k,
+                         (const unsigned long long*)d_bad, c0, d_tr ? d_tr + ntr : nullptr, cols,
+                         c0);
+      e = hipGetLastError();
+    }
+    double *ovg = o, *omean = o + (size_t)CB * 4 * k * n, *om2 = omean + (size_t)4 * k * 2 * C;
+    if (e == hipSuccess) {
+      hipLaunchKernelGGL(nmc_k_conv, dim3((unsigned)((nlb + 1) * 4 * k), CB), dim3(64), 0, st,
+                         (const double*)D, C, 4 * k, 0, n, n_valid, ovg, omean, om2);
+      e = hipGetLastError();
+    }
+    if (e == hipSuccess && x && c0 + k >= cols) rc = nmc_event_record(x, 7);
+    // quantity t of the batch: columns [t k, (t + 1) k) of D and of nmc_k_conv's outputs
+    for (int t = 0; t < 4 && e == hipSuccess && !rc; ++t) {
+      e = hipMemcpy2DAsync(vg + ((size_t)t * CB * cols + c0) * n, (size_t)cols * n * 8,
+                           ovg + (size_t)t * k * n, (size_t)4 * k * n * 8, (size_t)k * n * 8, CB,
+                           hipMemcpyDeviceToHost, st);
+      if (e == hipSuccess)
+        e = hipMemcpyAsync(mean + ((size_t)t * cols + c0) * 2 * C, omean + (size_t)t * k * 2 * C,
+                           (size_t)k * 2 * C * 8, hipMemcpyDeviceToHost, st);
+      if (e == hipSuccess)
+        e = hipMemcpyAsync(m2 + ((size_t)t * cols + c0) * 2 * C, om2 + (size_t)t * k * 2 * C,
+                           (size_t)k * 2 * C * 8, hipMemcpyDeviceToHost, st);
+      if (e == hipSuccess && derived)
+        e = hipMemcpy2DAsync(derived + ((size_t)t * n_rows * cols + c0) * C, (size_t)cols * C * 8,
+                             D + (size_t)t * k * C, (size_t)4 * k * C * 8, (size_t)k * C * 8,
+                             n_rows, hipMemcpyDeviceToHost, st);
+    }
+    // (the next batch overwrites D and the partials: the copies above are in stream order)
+  }
+  if (e == hipSuccess && !rc)
+    e = hipMemcpyAsync(nonfinite, d_bad, (size_t)cols * 8, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess && !rc && twice_rank)
+    e = hipMemcpyAsync(twice_rank, d_tr, 2 * ntr * 8, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess && !rc) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) rc = fail(-2, std::string("rank_partials: ") + hipGetErrorString(e));
+  hipStreamSynchronize(st);
+  hipFree(buf[0]); hipFree(buf[1]); hipFree(D); hipFree(o); hipFree(d_bad); hipFree(d_scratch);
+  hipFree(d_tr);
+  return rc;
+}
+
+int nmc_rank_partials(nmc_ctx* x, int row_begin, int n_rows, int n_valid, int col_batch,
+                      double* vg, double* mean, double* m2, int64_t* nonfinite) {
+  RES_PARK(x);
+  hipSetDevice(x->device);
+  const Dev& d = x->d;
+  if (int rc = rank_check(d.n_rows, x->C, d.cols, row_begin, n_rows, n_valid, col_batch)) return rc;
+  HIPCHK(hipStreamSynchronize(x->stream));
+  if (int rc = check_timeout(x)) return rc;
+  return rank_run(x, x->stream, d.samples, x->C, d.cols, row_begin, n_rows, n_valid, col_batch,
+                  vg, mean, m2, nonfinite, nullptr, nullptr, nullptr);
+}
+
+int nmc_rank_partials_of(int device, const double* xs, int rows, int cols, int C, int n_valid,
+                         int col_batch, double* vg, double* mean, double* m2, int64_t* nonfinite,
+                         double* derived, int64_t* twice_rank, double* zeta) {
+  if (rows < 1 || C < 1) return fail(-1, "rank_partials_of: need rows >= 1 and C >= 1");
+  if (int rc = rank_check(rows, C, cols, 0, rows, n_valid, col_batch)) return rc;
+  HIPCHK(hipSetDevice(device));
+  hipStream_t st;
+  HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+  double* dx = nullptr;
+  const size_t nx = (size_t)rows * cols * C;
+  hipError_t e = hipMalloc(&dx, nx * 8);
+  if (e == hipSuccess) e = hipMemcpyAsync(dx, xs, nx * 8, hipMemcpyHostToDevice, st);
+  int rc = e == hipSuccess
+               ? rank_run(nullptr, st, dx, C, cols, 0, rows, n_valid, col_batch, vg, mean, m2,
+                          nonfinite, derived, twice_rank, zeta)
+               : fail(-2, std::string("rank_partials_of: ") + hipGetErrorString(e));
   hipStreamSynchronize(st);
   hipFree(dx);
   hipStreamDestroy(st);

@@ -351,6 +351,38 @@ class Engine:
         return _summary.finish(raw["at_ranks"], raw["hdi"], raw["nonfinite"], raw["N"], names,
                                hdi_p)
 
+    def rank_partials(self, row_begin=0, n_rows=None, n_valid=None, col_batch=0):
+        """The rank-normalised diagnostics' partial sums over recorded rows [row_begin,
+        row_begin + n_rows) (n_rows even, two halves of n = n_rows / 2 >= 2 rows) and local
+        chains [0, n_valid), on the device from the sample store (nmc_rank_partials;
+        nestmc.rankdiag): (vg [4, CB, cols, n], mean [4, cols, 2, C], m2 [4, cols, 2, C],
+        nonfinite [cols]), the first axis the derived quantities z, zf, I05, I95.  col_batch:
+        the columns handled at a time (0: what fits the 1 GiB of temporary buffers); the
+        results do not depend on it."""
+        if n_rows is None:
+            n_rows = self.n_rows - row_begin
+        if n_valid is None:
+            n_valid = self.C
+        n_rows = int(n_rows)
+        n = max(n_rows // 2, 0)
+        vg = numpy.empty((4, (self.C + 63) // 64, self.cols, n))
+        mean = numpy.empty((4, self.cols, 2, self.C))
+        m2 = numpy.empty((4, self.cols, 2, self.C))
+        bad = numpy.empty(self.cols, dtype=numpy.int64)
+        check(self.lib.nmc_rank_partials(self.h, int(row_begin), n_rows, int(n_valid),
+                                         int(col_batch), dptr(vg), dptr(mean), dptr(m2),
+                                         bad.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
+        return vg, mean, m2, bad
+
+    def rank_diagnostics(self, names=None, row_begin=0, n_rows=None, n_valid=None, col_batch=0):
+        """The RankDiagnosticsResult (nestmc.rankdiag: rank-normalised and folded R-hat, bulk-
+        and tail-ESS per column) of this engine's chains over the given rows.  names: the
+        columns' names (default "col<k>")."""
+        from . import rankdiag as _rankdiag
+        vg, mean, m2, bad = self.rank_partials(row_begin, n_rows, n_valid, col_batch)
+        nv = self.C if n_valid is None else int(n_valid)
+        return _rankdiag.finish(vg, mean, m2, vg.shape[3], names, nv, bad)
+
     def eval_obs_ll(self):
         """Per-observation LL at the current state: [C, n_obs]."""
         out = numpy.empty((self.C, int(self.off[-1])))

@@ -26,6 +26,7 @@ from . import output
 from . import convergence as _conv
 from . import summary as _summary
 from . import loo as _loo
+from . import rankdiag as _rankdiag
 from . import waic as _waic
 from .engine import Engine
 from .families import is_family
@@ -66,7 +67,7 @@ def sample_posterior(nChains, nIter, nSamples, parameterName, nGroups, nResponse
                      seed=0, devices=None, rng="philox", chains=None, return_samples=False,
                      write_files=True, replay=None, process_per_device=False, _rank=None,
                      computeWaic=False, computeDiagnostics=False, computeSummary=False,
-                     computeLoo=False):
+                     computeLoo=False, computeRankDiagnostics=False):
     """Drop-in for posteriorSampling.samplePosterior (same positional/keyword API).
 
     Extra keyword-only options (all optional):
@@ -116,6 +117,16 @@ def sample_posterior(nChains, nIter, nSamples, parameterName, nGroups, nResponse
                  engine only: with several devices, chains= shards or process_per_device it
                  raises NotImplementedError before sampling starts (DESIGN section 10 has the
                  protocol that would lift this)
+      computeRankDiagnostics  after the loop, compute the rank-normalised and the folded
+                 split-R-hat, bulk-ESS and tail-ESS of every column (Vehtari et al. 2021)
+                 on the GPU from the device sample store (nestmc.rankdiag):
+                 outputDirectory/rank_diagnostics.csv, and "rank_diagnostics" (a
+                 nestmc.rankdiag.RankDiagnosticsResult) in the returned dict.  The recorded
+                 rows are cut into two halves: an odd number of them (or fewer than four)
+                 raises ValueError before sampling starts.  Ranks are global, so one engine
+                 only: several devices, chains= shards or process_per_device raise
+                 NotImplementedError before sampling starts (DESIGN section 10 has the
+                 protocol that would lift this)
     nProcesses sizes the host threads used for chain initialisation and CSV writing.
     """
     start_time = datetime.datetime.now()
@@ -138,6 +149,12 @@ def sample_posterior(nChains, nIter, nSamples, parameterName, nGroups, nResponse
         raise NotImplementedError(
             "computeLoo needs every chain in one engine: several devices, chains= shards and "
             "process_per_device are not supported yet")
+    if computeRankDiagnostics and ((devices is not None and len(list(devices)) > 1)
+                                   or chains is not None or process_per_device
+                                   or _rank is not None):
+        raise NotImplementedError(
+            "computeRankDiagnostics needs every chain in one engine (ranks are global): several "
+            "devices, chains= shards and process_per_device are not supported yet")
     names = tuple(parameterName)
     if len(names) != logLikelihoodFunction.n_params:
         raise ValueError("parameterName has %d names, the likelihood family has %d parameters"
@@ -172,6 +189,11 @@ def sample_posterior(nChains, nIter, nSamples, parameterName, nGroups, nResponse
         if n_rec % 2 or n_rec < 4:
             raise ValueError("computeDiagnostics cuts the %d recorded rows of a chain into two "
                              "halves: their number must be even and at least 4" % n_rec)
+    if computeRankDiagnostics:
+        n_rec = len(record_iterations(nIter, burn, thin))
+        if n_rec % 2 or n_rec < 4:
+            raise ValueError("computeRankDiagnostics cuts the %d recorded rows of a chain into "
+                             "two halves: their number must be even and at least 4" % n_rec)
     if computeSummary:
         n_val = len(record_iterations(nIter, burn, thin)) * \
             (nChains if chains is None else len(chains))
@@ -295,7 +317,8 @@ def sample_posterior(nChains, nIter, nSamples, parameterName, nGroups, nResponse
                             logger, chain_logs, start_time, rank_info,
                             compute_waic=bool(computeWaic), waic_dir=outputDirectory,
                             n_real=nChains, compute_conv=bool(computeDiagnostics),
-                            compute_summary=bool(computeSummary), compute_loo=bool(computeLoo))
+                            compute_summary=bool(computeSummary), compute_loo=bool(computeLoo),
+                            compute_rank=bool(computeRankDiagnostics))
     finally:
         for eng, _, _ in engines:
             eng.close()
@@ -434,7 +457,8 @@ def _summary_of(engines, rank_info, n_real, header):
 def _sample_loop(engines, nIter, burn, thin, names, G, partial, saveLogLikelihood, write_files,
                  sample_dir, threads, displayProgress, return_samples, logger, chain_logs,
                  start_time, rank_info=None, compute_waic=False, waic_dir=None,
-                 n_real=None, compute_conv=False, compute_summary=False, compute_loo=False):
+                 n_real=None, compute_conv=False, compute_summary=False, compute_loo=False,
+                 compute_rank=False):
     """The device loop, the per-observation LL rows and the sample files of
     sample_posterior (the caller closes the engines whatever happens here).  rank_info: a
     rank of process_per_device -- this rank writes its chains' logLikelihood files, rank 0
@@ -495,6 +519,11 @@ def _sample_loop(engines, nIter, burn, thin, names, G, partial, saveLogLikelihoo
         conv_result = _conv_of(engines, rank_info, n_real, header)
         if conv_result is not None and write_files:
             _conv.write_csv(conv_result, waic_dir)
+    rank_result = None
+    if compute_rank:   # (one engine, no padding chains: sample_posterior checked)
+        rank_result = engines[0][0].rank_diagnostics(header)
+        if write_files:
+            _rankdiag.write_csv(rank_result, waic_dir)
     summary_result = None
     if compute_summary:
         summary_result = _summary_of(engines, rank_info, n_real, header)
@@ -537,6 +566,8 @@ def _sample_loop(engines, nIter, burn, thin, names, G, partial, saveLogLikelihoo
             res["loo"] = loo_result
         if conv_result is not None:
             res["convergence"] = conv_result
+        if rank_result is not None:
+            res["rank_diagnostics"] = rank_result
         if summary_result is not None:
             res["summary"] = summary_result
             if conv_result is not None:

@@ -25,7 +25,7 @@ def samplePosterior(nChains, nIter, nSamples,
                     startWithMLE=False, startingPointValueRange=None,
                     nProcesses=1, displayProgress=True, loggingLevel="info",
                     computeWaic=False, computeDiagnostics=False, computeSummary=False,
-                    computeLoo=False, **gpu_options):
+                    computeLoo=False, computeRankDiagnostics=False, **gpu_options):
     """Sample the posterior of a nested model; samples go to outputDirectory/sample/.
 
     Arguments mirror the reference (posteriorSampling.py:28-145).  Keyword-only
@@ -38,7 +38,10 @@ def samplePosterior(nChains, nIter, nSamples,
     also sorts every column of the store on the GPU for its median, 95 % HDI, minimum and
     maximum (summary.csv; nestmc.summary).  computeLoo=True also computes PSIS-LOO with the
     Pareto k diagnostic of every observation on the GPU (loo.csv, loo_pointwise.csv;
-    nestmc.loo) -- one engine only.  Returns None like the reference unless
+    nestmc.loo) -- one engine only.  computeRankDiagnostics=True also computes the
+    rank-normalised and folded split-R-hat, bulk-ESS and tail-ESS of every column on the GPU
+    (rank_diagnostics.csv; nestmc.rankdiag) -- an even number of recorded rows and one engine
+    only.  Returns None like the reference unless
     return_samples=True.
     """
     return sample_posterior(nChains, nIter, nSamples, parameterName, nGroups,
@@ -50,4 +53,4 @@ def samplePosterior(nChains, nIter, nSamples,
                             loggingLevel=loggingLevel, computeWaic=computeWaic,
                             computeDiagnostics=computeDiagnostics,
                             computeSummary=computeSummary, computeLoo=computeLoo,
-                            **gpu_options)
+                            computeRankDiagnostics=computeRankDiagnostics, **gpu_options)
