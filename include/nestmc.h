@@ -390,6 +390,12 @@ int nmc_debug_rng(const uint32_t* ctr5, int n, uint32_t seed, double gamma_shape
  * host (on_device = 0, no GPU needed) or by a device kernel (on_device = 1); the two are
  * bit-identical by construction (IEEE add / mul / fma / div, rint, ldexp only).          */
 int nmc_debug_softplus(const double* x, int n, double* out, int on_device);
+/* The inverse of nmc_get_samples: writes recorded rows [row_begin, row_begin+n_rows) of the
+ * device sample store from in[row][col][C] (the store as set_schedule sized it; no sampling
+ * needed), so that the store's consumers -- nmc_obs_ll_rows, nmc_write_ll_csvs,
+ * nmc_waic_partials, nmc_loo, nmc_conv_partials, nmc_summary, nmc_rank_partials -- can be run
+ * on rows a sampler would not produce.  Nothing in the product path calls it.           */
+int nmc_debug_set_samples(nmc_ctx* ctx, int row_begin, int n_rows, const double* in);
 /* Diagnostic build only (make stamps -> libnestmc_stamps.so): shader-clock phase
  * stamps of the step kernel, [2 blocks][2 waves][8 iterations][16 slots]; n > 0
  * arms (zeroes) the buffer, out != NULL copies it back.  Error in the shipped lib. */

@@ -2411,6 +2411,22 @@ int nmc_debug_stamps(nmc_ctx* x, int n, uint64_t* out) {
 #endif
 }
 
+// nmc_get_samples' inverse: the store's consumers on rows the caller wrote (tests only)
+int nmc_debug_set_samples(nmc_ctx* x, int row_begin, int n_rows, const double* in) {
+  RES_PARK(x);
+  hipSetDevice(x->device);
+  const Dev& d = x->d;
+  if (row_begin < 0 || n_rows < 0 || row_begin + n_rows > d.n_rows)
+    return fail(-1, "row range out of bounds");
+  HIPCHK(hipStreamSynchronize(x->stream));
+  if (int rc = check_timeout(x)) return rc;
+  const size_t per = (size_t)d.cols * x->C;
+  if (n_rows)
+    HIPCHK(hipMemcpy(d.samples + (size_t)row_begin * per, in, (size_t)n_rows * per * 8,
+                     hipMemcpyHostToDevice));
+  return 0;
+}
+
 int nmc_debug_igamci(const double* a, const double* q, const double* lga, int n, double* out) {
   double *da, *dq, *dl, *dout;
   const size_t b = (n ? n : 1) * 8;

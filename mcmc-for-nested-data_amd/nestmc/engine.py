@@ -170,6 +170,16 @@ class Engine:
         check(self.lib.nmc_get_samples(self.h, row_begin, n_rows, dptr(out)))
         return out
 
+    def set_samples_raw(self, x, row_begin=0):
+        """Verification hook (nmc_debug_set_samples), the inverse of samples_raw: write
+        x [rows][cols][C] (float64, C-contiguous) into the device sample store from row
+        row_begin on.  The store is the one set_schedule sized; no product path calls this."""
+        if not (isinstance(x, numpy.ndarray) and x.dtype == numpy.float64 and x.ndim == 3
+                and x.shape[1:] == (self.cols, self.C) and x.flags["C_CONTIGUOUS"]):
+            raise ValueError("x must be a C-contiguous float64 array [rows][%d][%d]"
+                             % (self.cols, self.C))
+        check(self.lib.nmc_debug_set_samples(self.h, int(row_begin), x.shape[0], dptr(x)))
+
     def samples(self):
         """[C, rows, cols] chain-major (the oracle's row layout)."""
         return numpy.ascontiguousarray(numpy.transpose(self.samples_raw(), (2, 0, 1)))
