@@ -81,6 +81,13 @@ int nmc_device_count(int* n);
  * posteriorSampling.py:61-102, evaluated per row); include_dir = the library's csrc
  * directory (kernels.h and its parts, fam_user.h).  *family_id -> pass as nmc_create's
  * ll_family.
+ * 1 <= n_fields <= 64 and 1 <= n_params <= 16, else -1; nmc_create takes the family with
+ * an observation table of exactly that width and that many parameters.  Under partial
+ * pooling nmc_create also needs the workgroup's Gibbs state of all parameters in a CU's
+ * 160 KiB of LDS -- (14 + nleaf (9 + ntail)) n_params + 29 columns of 512 bytes, nleaf and
+ * ntail the leaves and the longest tail of numpy's pairwise sum over the groups: at most
+ * 12 parameters up to 128 groups, fewer over more leaves -- and refuses a model beyond it
+ * ("workgroup state exceeds the 160 KiB LDS of a CU") before anything is launched.
  * Errors carry the compiler log (nmc_last_error).                                  */
 int nmc_user_family_compile(const char* source, int n_fields, int n_params,
                             const char* include_dir, int* family_id);

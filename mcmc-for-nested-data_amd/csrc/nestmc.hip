@@ -768,7 +768,10 @@ int nmc_create(nmc_ctx** out, int device, int n_chains, int chain_base, int n_gr
   if (pooling < 0 || pooling > 2) return fail(-1, "invalid pooling");
   if (pooling == NMC_POOL_PARTIAL && n_groups < 2)
     return fail(-1, "partial pooling needs at least 2 groups (invgamma shape (G-1)/2 > 0)");
-  if (n_fields < 1 || n_fields > 9) return fail(-1, "n_fields must be 1..9");
+  // (built-in families are instantiated for 1..9 fields; a user family for the width it was
+  // compiled for, 1..64 -- nmc_user_family_compile -- which the shape check below holds it to)
+  if (n_fields < 1 || n_fields > (ll_family >= NMC_LL_USER_BASE ? 64 : 9))
+    return fail(-1, "n_fields must be 1..9 (1..64 for a user family)");
   if (group_offsets[0] != 0 || group_offsets[n_groups] != n_obs)
     return fail(-1, "group_offsets must start at 0 and end at n_obs");
   for (int g = 0; g < n_groups; ++g)

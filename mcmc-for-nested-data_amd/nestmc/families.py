@@ -192,6 +192,11 @@ class DeviceLikelihood(Family):
     the library's own flags: IEEE fp64, no contraction), then cached for the process.
     The kernels sum the per-row values in the same fixed order as the built-in families.
 
+    Limits: 1 to 64 fields and 1 to 16 parameters.  Under partial pooling the Gibbs update
+    keeps every parameter's state in the workgroup's 160 KiB of LDS, which holds at most 12
+    parameters up to 128 groups (9 to 12 by the group count modulo 8) and fewer over more
+    groups; the engine refuses a model beyond that when it is created.
+
     ``host_function(parameter[P][n]) -> ll[n]`` (optional) is the same model in the
     reference's calling convention; the host needs it only for ``startWithMLE`` (the
     Nelder-Mead objective, :1102-1141) -- every other evaluation runs on the device.

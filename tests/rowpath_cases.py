@@ -9,6 +9,10 @@ and tests/test_rowpath_reference.py.
   (per-row terms and their sum), with the formulas of nestmc/families.py, and returns
   beside each sum ``ref`` the same sum with every addend replaced by its absolute value,
   ``A`` -- the scale of ``tolerance``.
+* USER_CASES and the helpers after them are the same for runtime-compiled user families
+  (tests/test_gpu_user_rowpaths.py, tests/test_user_rowpath_cases.py): rows of up to 64
+  fields, the staged loop's chunk arithmetic, the step-kernel instance by pooling and Gibbs
+  hand-off, and the parameter limit of the partial-pooling workgroup state.
 """
 
 import collections
@@ -36,6 +40,18 @@ def row_block(nf):
     if nf <= 4:
         return 16 // nf
     return 4 if 32 // nf >= 4 else max(32 // nf, 1)
+
+
+def stage_rows(nf):
+    """rows.h nmc_stage_rows: rows per chunk of the staged loop -- whole row blocks within the
+    1008 bytes one 1 KiB DMA carries beside 16 B of alignment slack, at least one block."""
+    R = row_block(nf)
+    return R * ((1008 // (nf * 8)) // R) if (1008 // (nf * 8)) // R > 0 else R
+
+
+def stage_buf(nf):
+    """rows.h nmc_stage_buf: doubles of one staging buffer (whole 1 KiB DMAs)."""
+    return ((stage_rows(nf) * nf + 2) * 8 + 1023) // 1024 * 128
 
 
 def pairwise_leaves(G):
@@ -80,15 +96,24 @@ def predict(nf, sizes, nacc, P, pooling):
 # ---------------------------------------------------------------------------------------
 # cases
 # ---------------------------------------------------------------------------------------
-class RowCase:
-    """kind: linreg (sigma = 1 known), linreg_sig (sigma sampled), gauss, logistic."""
+def family_shape(kind, nf):
+    """(parameters, accumulator sets) of a case kind over nf fields."""
+    P = {"linreg_sig": nf + 1, "wide": 2}.get(kind, nf)
+    return P, (nf if kind == "gauss" else 1)
 
-    def __init__(self, name, kind, nf, sizes, pooling, lds, S, step_iters=8):
+
+class RowCase:
+    """kind: linreg (sigma = 1 known), linreg_sig (sigma sampled), gauss, logistic; the user
+    families of tests/user_models.py: wide (theta [a, b] over nf - 1 weighted fields), coef
+    (one coefficient per field)."""
+
+    def __init__(self, name, kind, nf, sizes, pooling, lds, S, step_iters=8, P=None):
         self.name, self.kind, self.nf, self.pooling = name, kind, nf, pooling
         self.sizes = [int(s) for s in sizes]
         self.lds, self.S, self.step_iters = lds, S, step_iters
-        self.P = nf + 1 if kind == "linreg_sig" else nf
-        self.nacc = nf if kind == "gauss" else 1
+        self.P, self.nacc = family_shape(kind, nf)
+        if P is not None:       # (a user family's parameters need not follow its fields)
+            self.P = P
         self.G = len(self.sizes)
 
     def __repr__(self):
@@ -105,8 +130,7 @@ class RowCase:
 
 def max_lds_rows(kind, nf, pooling, G):
     """The largest group that still has its rows in LDS (unsplit)."""
-    P = nf + 1 if kind == "linreg_sig" else nf
-    nacc = nf if kind == "gauss" else 1
+    P, nacc = family_shape(kind, nf)
     n = 65536 // (nf * 8)
     while n > 0 and not rows_fit_lds(n, nf, nacc, P, pooling == "partial", G):
         n -= 1
@@ -175,6 +199,124 @@ def _cases():
 CASES = _cases()
 BY_NAME = {c.name: c for c in CASES}
 
+
+# ---------------------------------------------------------------------------------------
+# user-family cases (tests/test_gpu_user_rowpaths.py, tests/test_user_rowpath_cases.py)
+# ---------------------------------------------------------------------------------------
+# the logistic cases of the matrix above, run again as a user family (user_models.user_logistic)
+USER_LOGISTIC = (["R-logistic-nf%d" % nf for nf in range(1, 10)] + ["scalar-logistic4-2049"]
+                 + ["staged-logistic%d-%s" % (nf, e) for nf in (5, 7, 8, 9)
+                    for e in ("first", "last")] + ["split-scalar", "split-staged"])
+# partial pooling beyond LDS, unsplit: the scalar-load loop (one group past 64 KiB of rows) and
+# the staged loop (seven parameters' hyper state leaves the rows no room in the 96 KiB carve,
+# whatever the group sizes; odd n_fields x odd row counts: odd double offsets)
+USER_PARTIAL = [RowCase("partial-scalar-logistic4", "logistic", 4, [2049, 0, 1, 17], "partial",
+                        False, 1),
+                RowCase("partial-staged-logistic7", "logistic", 7, [301, 0, 1, 13], "partial",
+                        False, 1)]
+# row widths no built-in family has: where nmc_row_block, nmc_stage_rows and nmc_stage_buf
+# change regime (R = 3, 2, 1; 32 / nf == 0; two rows filling the 1 KiB buffer to the last
+# double; one row per chunk), and 11 / 32, the far ends of R = 2 and R = 1
+WIDE_WIDTHS = (10, 11, 16, 17, 32, 33, 63, 64)
+COEF_NF = 16      # the P = 16 model: one coefficient per field
+
+
+def _wide_cases(kind, nf):
+    R = row_block(nf)
+    sizes = [1, R - 1, R, R + 1, 4 * R + 1, 37, 0]
+    cap = max_lds_rows(kind, nf, "none", len(sizes))
+    assert cap >= 37, (kind, nf, cap)
+    # one group just past the LDS row area, with an odd row count, among small odd groups
+    big = max_lds_rows(kind, nf, "none", 5) + 1
+    big += 1 - big % 2
+    tag = "%s%d" % (kind, nf)
+    return [RowCase(tag + "-lds", kind, nf, sizes, "none", True, 1),
+            RowCase(tag + "-staged-last", kind, nf, [0, 1, 3, 13, big], "none", False, 1),
+            RowCase(tag + "-staged-first", kind, nf, [big, 0, 1, 3, 13], "none", False, 1)]
+
+
+WIDE_CASES = {nf: _wide_cases("wide", nf) for nf in WIDE_WIDTHS}
+COEF_CASES = _wide_cases("coef", COEF_NF)
+USER_CASES = USER_PARTIAL + [c for nf in WIDE_WIDTHS for c in WIDE_CASES[nf]] + COEF_CASES
+BY_NAME.update({c.name: c for c in USER_CASES})
+
+
+def want_half(case, n_chains):
+    """choose_geometry: none/complete pooling on the paired loop (rows in LDS, <= 4 fields,
+    any family) whose 64-chain grid fills at most half the CUs runs 32 chains per workgroup."""
+    blocks = -(-n_chains // 64)
+    return (case.pooling != "partial" and case.S == 1 and case.lds and case.nf <= 4
+            and blocks * case.G * 2 <= NCU)
+
+
+def run_columns(nf, n_member, nacc, P, partial, G, lds, payload=False):
+    """ctx.h lds_bytes_for in 512-byte columns: the carve, the two Gibbs payload buffers
+    (SYNC_LDS) and the member's rows or, beyond LDS with more than 4 fields, every wave's two
+    staging buffers (choose_geometry's wave count: control + one per 64 rows + the Gibbs wave,
+    at most 8)."""
+    w = 1 + (n_member + 63) // 64
+    w = min(8, w + 1 if partial and w >= 2 else w)
+    doubles = n_member * nf if lds else (0 if nf <= 4 else w * 2 * stage_buf(nf))
+    return (carve_columns(nacc, P, partial, G) + (2 * (G + 1) if partial and payload else 0)
+            + ((doubles + 63) // 64 + 1 if doubles else 0))
+
+
+LDS_CU = 160 * 1024       # choose_kernel refuses a workgroup state beyond it
+
+
+def user_step_kernel(case, n_chains, env=None):
+    """(kernel name, persistent) nmc_launch_config reports for a user family on ``case``:
+    choose_geometry's mode by pooling, Gibbs hand-off and NMC_PERSIST / NMC_HALF / NMC_ROWS,
+    with the rows suffix of predict().  A user family never sweeps."""
+    env = env or {}
+    p = case.path
+    assert (p.lds, p.S) == (case.lds, case.S), (case.name, p)
+    persistent = True     # (none / complete pooling: one launch runs all the iterations)
+    if case.pooling != "partial":
+        half = (want_half(case, n_chains) and env.get("NMC_HALF") != "0"
+                and env.get("NMC_ROWS") != "bcast")
+        mode = "HALF" if half else "NOPOOL"
+    else:
+        args = (case.nf, p.n_member, case.nacc, case.P, True, case.G, p.lds)
+        assert run_columns(*args) * 512 <= LDS_CU, case.name
+        w = 1 + (p.n_member + 63) // 64
+        naux = w + 1 >= 3 and len(pairwise_leaves(case.G)) <= 4
+        hlds = naux and case.G <= 128 and run_columns(*args, payload=True) * 512 <= LDS_CU
+        persistent = env.get("NMC_PERSIST") != "0"
+        mode = ("LAUNCH" if not persistent else
+                "SYNC_REG" if hlds and case.G <= 64 else "SYNC_LDS" if hlds else "SYNC")
+    return ("nmc_k_run<FamUser, NMC_MODE_%s, %s>" % (mode, "true" if p.lds else "false"),
+            persistent)
+
+
+def user_gibbs_mode(fam, sizes):
+    """gibbs_mode for a user family: nmc_k_sweep takes built-in families only
+    (choose_geometry's sweep_want), so more than one numpy leaf runs nmc_k_run's all-wave
+    update."""
+    kernel, modes = gibbs_mode(fam, sizes)
+    if kernel == "nmc_k_sweep<":
+        return "nmc_k_run<", ("NMC_MODE_SYNC", "NMC_MODE_LAUNCH")
+    return kernel, modes
+
+
+def gibbs_persistent(G, C):
+    """Whether the partial-pooling grid of C chains over G small groups is co-resident, and so
+    runs persistent: the workgroup states of the user Gibbs cases are beyond 53 KiB, where the
+    residency rule (ctx.h nmc_safe_blocks over the occupancy of 160 KiB of LDS) keeps one
+    workgroup per CU."""
+    return -(-C // 64) * G <= NCU
+
+
+def max_partial_params(nf, n_member, G):
+    """The largest n_params whose partial-pooling workgroup state (rows beyond LDS where the
+    96 KiB carve has no room for them) fits the CU's 160 KiB: what choose_kernel accepts."""
+    best = 0
+    for P in range(1, 17):
+        lds = rows_fit_lds(n_member, nf, 1, P, True, G)
+        if run_columns(nf, n_member, 1, P, True, G, lds) * 512 <= LDS_CU:
+            best = P
+    return best
+
 Model = collections.namedtuple("Model", "fam priors truth post_sd")
 
 
@@ -195,6 +337,20 @@ def model(name):
         fam = GaussianMean.from_groups(mu, sd, c.sizes)
         truth = mu
         post = 1.0 / numpy.sqrt(nn[None, :] / sd[:, None] ** 2 + prior_prec)
+    elif c.kind in ("wide", "coef"):
+        import user_models
+        x = r.normal(size=(n, nf - 1))
+        if c.kind == "wide":
+            w = user_models.wide_weights(nf)
+            truth = numpy.vstack([r.normal(size=G), r.normal(1.0, 0.5, size=G)])
+            y = truth[0, grp] + truth[1, grp] * (x @ w) + r.normal(size=n)
+            fam = user_models.wide_family(numpy.hstack([x, y[:, None]]))
+            post = 1.0 / numpy.sqrt(nn[None, :] * numpy.array([[1.0], [w @ w]]) + prior_prec)
+        else:
+            truth = r.normal(0, 0.5, size=(nf, G))
+            y = truth[0, grp] + numpy.sum(x * truth[1:, grp].T, axis=1) + r.normal(size=n)
+            fam = user_models.coef_family(numpy.hstack([x, y[:, None]]))
+            post = 1.0 / numpy.sqrt(nn[None, :] + prior_prec) * numpy.ones((nf, 1))
     else:
         K = nf - 1
         X = numpy.hstack([numpy.ones((n, 1)), r.normal(size=(n, K))])
@@ -217,7 +373,7 @@ def model(name):
                 post = numpy.vstack([post, ps[None, :]])
     priors = None
     if c.pooling != "partial":
-        priors = [scipy.stats.norm(0, 10)] * nf
+        priors = [scipy.stats.norm(0, 10)] * (2 if c.kind == "wide" else nf)
         if c.kind == "linreg_sig":
             priors = priors + [scipy.stats.gamma(2)]
     assert fam.n_fields == nf and fam.n_params == c.P, (fam.n_fields, fam.n_params)
@@ -273,6 +429,10 @@ def reference(fam, sizes, theta):
         if rows.shape[0] == 0:
             continue
         th = theta[:, :, g].astype(LD)                         # [C, P]
+        if getattr(fam, "model", None) is not None:            # user_models wide / coef
+            ll, a = _user_rows(fam, rows, th)
+            ref[:, g], A[:, g] = ll.sum(axis=1), a.sum(axis=1)
+            continue
         if isinstance(fam, GaussianMean):
             sd = fam.sd.astype(LD)
             e = (th[:, None, :] - rows[None, :, :]) / sd        # [C, n, P]
@@ -296,6 +456,44 @@ def reference(fam, sizes, theta):
         ra = (numpy.abs(b0)[:, None] + (numpy.abs(b)[:, None, :] * numpy.abs(x)[None]).sum(axis=2)
               + numpy.abs(y)[None, :]) / sig
         A[:, g] = ((ra * ra) / 2 + LOG_C_LD + numpy.abs(numpy.log(sig))).sum(axis=1)
+    return ref, A
+
+
+def _user_rows(fam, rows, th):
+    """Per-row terms of the user models of tests/user_models.py in longdouble: rows [n, nf],
+    th [C, P] -> (ll, a), each [C, n].  Both are ll = -(y - eta)^2 / 2; a takes the residual
+    as |a| + |b| sum |w_j x_j| + |y| (wide) or |b_0| + sum |b_j x_j| + |y| (coef) before
+    squaring, like the regression's."""
+    import user_models
+    nf = rows.shape[1]
+    x, y = rows[:, :nf - 1], rows[:, nf - 1]
+    if fam.model == "wide":
+        w = user_models.wide_weights(nf).astype(LD)
+        # (the weights are the float64 constants the device holds, products in field order)
+        eta = th[:, 0, None] + th[:, 1, None] * (x * w[None, :]).sum(axis=1)[None, :]
+        ra = (numpy.abs(th[:, 0, None]) + numpy.abs(th[:, 1, None])
+              * numpy.abs(x * w[None, :]).sum(axis=1)[None, :] + numpy.abs(y)[None, :])
+    else:
+        assert fam.model == "coef", fam.model
+        eta = th[:, 0, None] + (th[:, None, 1:] * x[None, :, :]).sum(axis=2)
+        ra = (numpy.abs(th[:, 0, None]) + (numpy.abs(th[:, None, 1:]) * numpy.abs(x)[None]).sum(axis=2)
+              + numpy.abs(y)[None, :])
+    e = y[None, :] - eta
+    return -(e * e) / 2, (ra * ra) / 2
+
+
+def reference_rows(fam, sizes, theta):
+    """Per-observation log-likelihoods of a user model at theta [C, P, G] in longdouble:
+    (ref, A), each [C, n_obs]."""
+    theta = numpy.asarray(theta)
+    obs = numpy.asarray(fam.obs()).astype(LD)
+    off = numpy.concatenate([[0], numpy.cumsum(sizes)])
+    ref = numpy.zeros((theta.shape[0], obs.shape[0]), LD)
+    A = numpy.zeros_like(ref)
+    for g in range(theta.shape[2]):
+        if off[g + 1] > off[g]:
+            ref[:, off[g]:off[g + 1]], A[:, off[g]:off[g + 1]] = _user_rows(
+                fam, obs[off[g]:off[g + 1]], theta[:, :, g].astype(LD))
     return ref, A
 
 
@@ -426,6 +624,11 @@ def gibbs_model(kind, G):
         b0, b1 = r.normal(size=G), r.normal(2, 1, size=G)
         y = b0[grp] + b1[grp] * x + r.normal(size=n)
         return LinearRegression.simple(x, y, sigma=1.0), sizes
+    if kind == "logistic4":
+        X = numpy.hstack([numpy.ones((n, 1)), r.normal(size=(n, 3))])
+        th = r.normal(0, 0.5, size=(G, 4))
+        p = 1 / (1 + numpy.exp(-numpy.sum(X * th[grp], axis=1)))
+        return Logistic(X, (r.uniform(size=n) < p).astype(float)), sizes
     return GaussianMean.from_groups(r.normal(size=(1, G)), [0.8], sizes), sizes
 
 
@@ -444,3 +647,64 @@ def gibbs_mode(fam, sizes):
     if G <= 128 and cols * 512 <= 160 * 1024:
         return "nmc_k_run<", ("NMC_MODE_SYNC_REG" if G <= 64 else "NMC_MODE_SYNC_LDS",)
     return "nmc_k_run<", ("NMC_MODE_SYNC", "NMC_MODE_LAUNCH")
+
+
+# ---------------------------------------------------------------------------------------
+# the oracle-compared runs of the user-family tests, defined once: the GPU tests run them
+# (tests/test_gpu_user_rowpaths.py) and the CPU tests check from the oracle's trace alone that
+# they accept a fair share of their proposals and decide none by a near tie
+# (tests/test_user_rowpath_cases.py)
+# ---------------------------------------------------------------------------------------
+USER_C = 65               # one full chain block and a partly filled second one
+USER_GIBBS_G = (64, 65, 96, 100, 128, 129, 513)
+Run = collections.namedtuple("Run", "fam sizes state sel n_iter seed base kw")
+
+
+def oracle_sel(C=USER_C):
+    return numpy.array([0, 1, C - 1])
+
+
+def chain_run(name, C=USER_C):
+    """test_chain_matches_oracle's run of a none-pooling case: a start near the posterior with
+    proposal scales of 2.4 posterior sd, no stored LL (the reference's own start)."""
+    from oracle import restatement as rs
+    case, m = BY_NAME[name], model(name)
+    value, lp, mu, s2, scale = start(name, C)
+    assert case.pooling == "none"
+    st = rs.State(value, lp, numpy.full((C, case.G), numpy.nan), mu, s2)
+    kw = dict(pooling=case.pooling, priors=m.priors, tune_interval=3, scale=scale)
+    return Run(m.fam, case.sizes, st, oracle_sel(C), case.step_iters, 77, 5, kw)
+
+
+def gibbs_run(G, C=USER_C):
+    """test_gibbs_geometry_edges' run for the four-parameter logistic over G small groups;
+    every chain is compared."""
+    from gpu_cases import partial_state
+    fam, sizes = gibbs_model("logistic4", G)
+    st, _ = partial_state(fam, sizes, C, fam.n_params)
+    # (the Philox seed is chosen on the CPU: with seed 13 the oracle decides one of the 800 000
+    # steps of the 513 groups by a margin of 7e-8)
+    return Run(fam, sizes, st, numpy.arange(C), 10 if G <= 136 else 6, 14 if G == 513 else 13,
+               2, dict(tune_interval=3))
+
+
+def param_limit_run(P, C=USER_C):
+    """A P-parameter polynomial (user_models.poly_family: two fields) over G = 8 groups of 20
+    rows under partial pooling: the parameter limit of the workgroup state."""
+    import user_models
+    from gpu_cases import partial_state
+    G, n = 8, 20
+    r = numpy.random.RandomState(500 + P)
+    x = r.uniform(-1, 1, size=G * n)
+    c = r.normal(0, 0.5, size=(G, P))
+    y = numpy.sum(c[numpy.repeat(numpy.arange(G), n)] * x[:, None] ** numpy.arange(P), axis=1)
+    fam = user_models.poly_family(x, y + 0.5 * r.normal(size=G * n), P)
+    st, _ = partial_state(fam, [n] * G, C, P, spread=0.3)
+    return Run(fam, [n] * G, st, oracle_sel(C), 8, 21, 1, dict(tune_interval=3))
+
+
+def run_oracle_of(run):
+    """(flags, proposal LLs, rows, least decision margin) of the oracle on run.sel."""
+    from gpu_cases import run_oracle
+    return run_oracle(FastNested(run.fam, run.sizes), run.state, run.sel, run.sel + run.base,
+                      run.n_iter, run.seed, **run.kw)
