@@ -316,6 +316,28 @@ int nmc_rank_partials_of(int device, const double* x, int rows, int cols, int C,
                          int col_batch, double* vg, double* mean, double* m2,
                          int64_t* nonfinite, double* derived, int64_t* twice_rank,
                          double* zeta);
+/* Group rankings and pairwise comparisons of a parameter's G group values (the league table
+ * of a multilevel model, Goldstein and Spiegelhalter 1996; the definitions are
+ * nestmc/groupcmp.py's docstring) over recorded rows [row_begin, row_begin + n_rows) and local
+ * chains [0, n_valid), on the device from the sample store as it lies: the values are the
+ * recorded ones of posteriorSampling.py:640-659, 771-787; the counts themselves have no
+ * counterpart in the reference.  Per sample s = (row, chain) and parameter p, theta_g is store
+ * column p (G + pc) + pc + g (pc = 2 under partial pooling: _mu and _sigma2 are skipped);
+ * comparisons are fp64 comparisons (NaN false both ways, -0.0 == +0.0):
+ *   hist[p][g][r] = #{s : #{h : theta_h < theta_g} = r}      (0-based strict rank)
+ *   wins[p][g][h] = #{s : theta_g > theta_h}
+ *   nonfinite[p]  = #{(s, g) : theta_g is NaN or +-inf}      (callers treat a count as an error)
+ * Integer counts only (csrc/grouporder.h): the words do not depend on the row window's
+ * slicing, and several engines' or ranks' counts add.  The call allocates and frees the two
+ * device count arrays (2 P G^2 4 bytes).  G >= 2, n_rows >= 1 and the rows inside the
+ * schedule's, 1 <= n_valid <= C, n_rows * n_valid < 2^31, else -1 and nothing is written.
+ * Event slots 4 and 5 bracket the kernel.                                              */
+int nmc_group_order(nmc_ctx* ctx, int row_begin, int n_rows, int n_valid, uint32_t* hist,
+                    uint32_t* wins, int64_t* nonfinite);
+/* The same over a host array x[rows][cols][C] in the store's layout (all of its rows),
+ * cols = P * (G + 2 * partial), partial 0 or 1, copied to `device`; needs no context.   */
+int nmc_group_order_of(int device, const double* x, int rows, int P, int G, int partial, int C,
+                       int n_valid, uint32_t* hist, uint32_t* wins, int64_t* nonfinite);
 
 /* Timing on the context's stream (hipEvents). */
 int nmc_event_record(nmc_ctx* ctx, int slot);                 /* slot 0..15 */

@@ -29,6 +29,7 @@
 #include "sortcol.h"       // nmc_k_sort_*: the columns' sort and order statistics
 #include "psis.h"          // nmc_k_psis: PSIS-LOO over a sorted log-likelihood column
 #include "rankz.h"         // nmc_k_rank_transform: values to their ranks' normal scores
+#include "grouporder.h"    // nmc_k_group_order: the groups' rank histogram and pairwise wins
 
 #define NMC_VERSION "nestmc 0.2.0 (gfx950)"
 
@@ -2011,6 +2012,115 @@ int nmc_rank_partials_of(int device, const double* xs, int rows, int cols, int C
                ? rank_run(nullptr, st, dx, C, cols, 0, rows, n_valid, col_batch, vg, mean, m2,
                           nonfinite, derived, twice_rank, zeta)
                : fail(-2, std::string("rank_partials_of: ") + hipGetErrorString(e));
+  hipStreamSynchronize(st);
+  hipFree(dx);
+  hipStreamDestroy(st);
+  return rc;
+}
+
+// Group rankings and pairwise comparisons (grouporder.h; nestmc/groupcmp.py has the
+// definitions; include/nestmc.h) -- no reference counterpart.  One kernel over the store; the
+// two count arrays [P][G][G] are allocated, zeroed and freed by the call.
+static int go_check(int rows, int C, int P, int G, int row_begin, int n_rows, int n_valid) {
+  if (P < 1 || G < 2) return fail(-1, "group_order: needs at least two groups");
+  if (n_rows < 1 || row_begin < 0 || row_begin > rows - n_rows)
+    return fail(-1, "group_order: row range out of bounds");
+  if (n_valid < 1 || n_valid > C) return fail(-1, "n_valid must be in 1..n_chains");
+  if ((int64_t)n_rows * n_valid >= ((int64_t)1 << 31))
+    return fail(-1, "group_order: 2^31 or more samples");
+  return 0;
+}
+
+// x: the context whose event slots 4 / 5 bracket the kernel, or NULL.
+static int go_run(nmc_ctx* x, hipStream_t st, const double* samples, int C, int cols, int P,
+                  int G, int pc, int row_begin, int n_rows, int n_valid, uint32_t* hist,
+                  uint32_t* wins, int64_t* nonfinite) {
+  const int nw = nmc_go_waves(G);
+  const bool direct = nw == 0;
+  const int wpg = direct ? 1 : nw;                        // waves of a workgroup
+  const int ntile = (G + NMC_GO_T * wpg - 1) / (NMC_GO_T * wpg);
+  const int CBv = (n_valid + 63) / 64;
+  // row slices: enough workgroups to fill the device, at least 8 rows each (the flush of a
+  // workgroup's counts costs about as many atomics as 2 rows' compares)
+  const int64_t tasks = (int64_t)P * ntile * CBv;
+  int64_t nslice = std::min<int64_t>((n_rows + 7) / 8, (4096 + tasks - 1) / tasks);
+  nslice = std::max<int64_t>(1, std::min<int64_t>(nslice, 65535));
+  const int rps = (int)((n_rows + nslice - 1) / nslice);
+  nslice = (n_rows + rps - 1) / rps;
+  if (CBv > 65535 || (int64_t)P * ntile > 0x7fffffff)
+    return fail(-1, "group_order: too many chain blocks or group tiles");
+  const size_t lds = direct ? 0 : (size_t)wpg * 2 * NMC_GO_T * G * 4;
+  const size_t nc = (size_t)P * G * G;
+  uint32_t* o = nullptr;
+  unsigned long long* d_bad = nullptr;
+  hipError_t e = hipSuccess;
+  if (lds > 64 * 1024)
+    e = hipFuncSetAttribute((const void*)nmc_k_group_order<false>,
+                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (e == hipSuccess) e = hipMalloc(&o, 2 * nc * 4);
+  if (e == hipSuccess) e = hipMalloc(&d_bad, (size_t)P * 8);
+  if (e == hipSuccess) e = hipMemsetAsync(o, 0, 2 * nc * 4, st);
+  if (e == hipSuccess) e = hipMemsetAsync(d_bad, 0, (size_t)P * 8, st);
+  int rc = 0;
+  if (e == hipSuccess && x) rc = nmc_event_record(x, 4);
+  if (e == hipSuccess && !rc) {
+    const dim3 grid((unsigned)(P * ntile), (unsigned)CBv, (unsigned)nslice), blk(wpg * 64);
+    if (direct)
+      hipLaunchKernelGGL(nmc_k_group_order<true>, grid, blk, 0, st, samples, C, cols, P, G, pc,
+                         ntile, row_begin, n_rows, rps, n_valid, o, o + nc, d_bad);
+    else
+      hipLaunchKernelGGL(nmc_k_group_order<false>, grid, blk, lds, st, samples, C, cols, P, G,
+                         pc, ntile, row_begin, n_rows, rps, n_valid, o, o + nc, d_bad);
+    e = hipGetLastError();
+    if (e == hipSuccess && x) rc = nmc_event_record(x, 5);
+  }
+  // (staged: the caller's arrays are written only when everything before has succeeded)
+  std::vector<unsigned long long> bad(P);
+  if (e == hipSuccess && !rc)
+    e = hipMemcpyAsync(bad.data(), d_bad, (size_t)P * 8, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess && !rc) e = hipStreamSynchronize(st);
+  if (e == hipSuccess && !rc) e = hipMemcpy(hist, o, nc * 4, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && !rc) e = hipMemcpy(wins, o + nc, nc * 4, hipMemcpyDeviceToHost);
+  if (e != hipSuccess) rc = fail(-2, std::string("group_order: ") + hipGetErrorString(e));
+  if (!rc)
+    for (int p = 0; p < P; ++p) nonfinite[p] = (int64_t)bad[p];
+  hipStreamSynchronize(st);
+  hipFree(o); hipFree(d_bad);
+  return rc;
+}
+
+int nmc_group_order(nmc_ctx* x, int row_begin, int n_rows, int n_valid, uint32_t* hist,
+                    uint32_t* wins, int64_t* nonfinite) {
+  RES_PARK(x);
+  hipSetDevice(x->device);
+  const Dev& d = x->d;
+  if (int rc = go_check(d.n_rows, x->C, x->P, x->G, row_begin, n_rows, n_valid)) return rc;
+  HIPCHK(hipStreamSynchronize(x->stream));
+  if (int rc = check_timeout(x)) return rc;
+  const int pc = x->pooling == NMC_POOL_PARTIAL ? 2 : 0;
+  return go_run(x, x->stream, d.samples, x->C, d.cols, x->P, x->G, pc, row_begin, n_rows,
+                n_valid, hist, wins, nonfinite);
+}
+
+int nmc_group_order_of(int device, const double* xs, int rows, int P, int G, int partial, int C,
+                       int n_valid, uint32_t* hist, uint32_t* wins, int64_t* nonfinite) {
+  if (rows < 1 || C < 1) return fail(-1, "group_order_of: need rows >= 1 and C >= 1");
+  if (partial != 0 && partial != 1) return fail(-1, "group_order_of: partial must be 0 or 1");
+  if (int rc = go_check(rows, C, P, G, 0, rows, n_valid)) return rc;
+  const int pc = 2 * partial;
+  if ((int64_t)P * (G + pc) > 0x7fffffff) return fail(-1, "group_order_of: too many columns");
+  const int cols = P * (G + pc);
+  HIPCHK(hipSetDevice(device));
+  hipStream_t st;
+  HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+  double* dx = nullptr;
+  const size_t nx = (size_t)rows * cols * C;
+  hipError_t e = hipMalloc(&dx, nx * 8);
+  if (e == hipSuccess) e = hipMemcpyAsync(dx, xs, nx * 8, hipMemcpyHostToDevice, st);
+  int rc = e == hipSuccess
+               ? go_run(nullptr, st, dx, C, cols, P, G, pc, 0, rows, n_valid, hist, wins,
+                        nonfinite)
+               : fail(-2, std::string("group_order_of: ") + hipGetErrorString(e));
   hipStreamSynchronize(st);
   hipFree(dx);
   hipStreamDestroy(st);

@@ -393,6 +393,39 @@ class Engine:
         nv = self.C if n_valid is None else int(n_valid)
         return _rankdiag.finish(vg, mean, m2, vg.shape[3], names, nv, bad)
 
+    def group_order_counts(self, row_begin=0, n_rows=None, n_valid=None):
+        """The groups' rank histogram and pairwise win counts over recorded rows [row_begin,
+        row_begin + n_rows) and local chains [0, n_valid), counted on the device from the
+        sample store (nmc_group_order; nestmc.groupcmp has the definitions): a dict of hist
+        [P, G, G], wins [P, G, G], nonfinite [P] (int64) and n_samples."""
+        if n_rows is None:
+            n_rows = self.n_rows - row_begin
+        if n_valid is None:
+            n_valid = self.C
+        n_rows, n_valid = int(n_rows), int(n_valid)
+        hist = numpy.empty((self.P, self.G, self.G), dtype=numpy.uint32)
+        wins = numpy.empty((self.P, self.G, self.G), dtype=numpy.uint32)
+        bad = numpy.empty(self.P, dtype=numpy.int64)
+        u32 = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))   # noqa: E731
+        check(self.lib.nmc_group_order(self.h, int(row_begin), n_rows, n_valid, u32(hist),
+                                       u32(wins),
+                                       bad.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
+        return dict(hist=hist.astype(numpy.int64), wins=wins.astype(numpy.int64), nonfinite=bad,
+                    n_samples=n_rows * n_valid)
+
+    def group_comparison(self, names=None, row_begin=0, n_rows=None, n_valid=None):
+        """The GroupComparisonResult (nestmc.groupcmp: every group's rank distribution and
+        P(theta_g > theta_h) of every pair, per parameter) of this engine's chains over the
+        given rows.  names: the P parameters' names (default "p<k>").  A group value that is
+        not finite is an error."""
+        from . import groupcmp as _groupcmp
+        raw = self.group_order_counts(row_begin, n_rows, n_valid)
+        self.group_nonfinite = int(raw["nonfinite"].sum())
+        if self.group_nonfinite:
+            raise _lib.NestmcError("group comparison: %d group values were not finite"
+                                   % self.group_nonfinite)
+        return _groupcmp.finish(raw["hist"], raw["wins"], raw["n_samples"], names)
+
     def eval_obs_ll(self):
         """Per-observation LL at the current state: [C, n_obs]."""
         out = numpy.empty((self.C, int(self.off[-1])))

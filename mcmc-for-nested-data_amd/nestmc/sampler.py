@@ -24,6 +24,7 @@ import numpy
 from . import _lib
 from . import output
 from . import convergence as _conv
+from . import groupcmp as _groupcmp
 from . import summary as _summary
 from . import loo as _loo
 from . import rankdiag as _rankdiag
@@ -67,7 +68,8 @@ def sample_posterior(nChains, nIter, nSamples, parameterName, nGroups, nResponse
                      seed=0, devices=None, rng="philox", chains=None, return_samples=False,
                      write_files=True, replay=None, process_per_device=False, _rank=None,
                      computeWaic=False, computeDiagnostics=False, computeSummary=False,
-                     computeLoo=False, computeRankDiagnostics=False):
+                     computeLoo=False, computeRankDiagnostics=False,
+                     computeGroupComparison=False):
     """Drop-in for posteriorSampling.samplePosterior (same positional/keyword API).
 
     Extra keyword-only options (all optional):
@@ -127,6 +129,17 @@ def sample_posterior(nChains, nIter, nSamples, parameterName, nGroups, nResponse
                  only: several devices, chains= shards or process_per_device raise
                  NotImplementedError before sampling starts (DESIGN section 10 has the
                  protocol that would lift this)
+      computeGroupComparison  after the loop, count on the GPU from the device sample store,
+                 per parameter, every group's rank among the G groups in every sample and
+                 every ordered pair's wins (nestmc.groupcmp: the league table of a multilevel
+                 model): outputDirectory/group_ranking.csv (mean and median rank with a 95 %
+                 rank interval, the probabilities of being lowest and highest) and
+                 group_pairwise.csv (P(theta_g > theta_h)), and "group_comparison" (a
+                 nestmc.groupcmp.GroupComparisonResult) in the returned dict.  The counts are
+                 integers: several engines (devices=[...]), chains= shards merged by the
+                 caller and the ranks of process_per_device give the one engine's numbers bit
+                 for bit.  pooling="complete" has one group and raises ValueError before
+                 sampling starts
     nProcesses sizes the host threads used for chain initialisation and CSV writing.
     """
     start_time = datetime.datetime.now()
@@ -155,6 +168,9 @@ def sample_posterior(nChains, nIter, nSamples, parameterName, nGroups, nResponse
         raise NotImplementedError(
             "computeRankDiagnostics needs every chain in one engine (ranks are global): several "
             "devices, chains= shards and process_per_device are not supported yet")
+    if computeGroupComparison and (pooling == "complete" or nGroups < 2):
+        raise ValueError("computeGroupComparison compares a parameter's groups with each other: "
+                         "it needs at least two groups (pooling='complete' has one)")
     names = tuple(parameterName)
     if len(names) != logLikelihoodFunction.n_params:
         raise ValueError("parameterName has %d names, the likelihood family has %d parameters"
@@ -237,7 +253,8 @@ def sample_posterior(nChains, nIter, nSamples, parameterName, nGroups, nResponse
                   loggingLevel=loggingLevel, seed=seed, rng=rng,
                   return_samples=return_samples, write_files=write_files,
                   computeWaic=computeWaic, computeDiagnostics=computeDiagnostics,
-                  computeSummary=computeSummary)
+                  computeSummary=computeSummary,
+                  computeGroupComparison=computeGroupComparison)
         res = ranks.run_per_device(kw, devices)
         _finish_log(logger, [], start_time, displayProgress)
         return res
@@ -318,7 +335,8 @@ def sample_posterior(nChains, nIter, nSamples, parameterName, nGroups, nResponse
                             compute_waic=bool(computeWaic), waic_dir=outputDirectory,
                             n_real=nChains, compute_conv=bool(computeDiagnostics),
                             compute_summary=bool(computeSummary), compute_loo=bool(computeLoo),
-                            compute_rank=bool(computeRankDiagnostics))
+                            compute_rank=bool(computeRankDiagnostics),
+                            compute_group=bool(computeGroupComparison))
     finally:
         for eng, _, _ in engines:
             eng.close()
@@ -424,6 +442,32 @@ def _conv_of(engines, rank_info, n_real, header):
     return _conv.finish(vg, mean, m2, n, header)
 
 
+def _group_of(engines, rank_info, n_real, names):
+    """computeGroupComparison: every engine's integer counts over all recorded rows and its
+    real chains (padding chains, ids >= n_real, excluded; an engine with none adds zeros),
+    merged in engine order; the ranks of process_per_device send theirs over the host group
+    and rank 0 merges them in rank order (the other ranks: None).  A group value that is not
+    finite is an error."""
+    eng0 = engines[0][0]
+    P, G = eng0.P, eng0.G
+    parts = []
+    for eng, _, ids in engines:
+        n_valid = sum(1 for c in ids if c < n_real)
+        parts.append(eng.group_order_counts(n_valid=n_valid) if n_valid > 0
+                     else _groupcmp.zero_counts(P, G))
+    part = _groupcmp.merge(parts)
+    if rank_info is not None:
+        got = rank_info["hg"].gather(numpy.ascontiguousarray(_groupcmp.pack(part)).tobytes())
+        if rank_info["rank"] != 0:
+            return None
+        part = _groupcmp.merge([_groupcmp.unpack(numpy.frombuffer(b, dtype=numpy.int64), P, G)
+                                for b in got])
+    bad = int(part["nonfinite"].sum())
+    if bad:
+        raise _lib.NestmcError("group comparison: %d group values were not finite" % bad)
+    return _groupcmp.finish(part["hist"], part["wins"], part["n_samples"], names)
+
+
 def _summary_of(engines, rank_info, n_real, header):
     """computeSummary: one engine sorts its store's columns and only per-column results leave
     the device.  Several engines, and the ranks of process_per_device, each sort the values of
@@ -458,7 +502,7 @@ def _sample_loop(engines, nIter, burn, thin, names, G, partial, saveLogLikelihoo
                  sample_dir, threads, displayProgress, return_samples, logger, chain_logs,
                  start_time, rank_info=None, compute_waic=False, waic_dir=None,
                  n_real=None, compute_conv=False, compute_summary=False, compute_loo=False,
-                 compute_rank=False):
+                 compute_rank=False, compute_group=False):
     """The device loop, the per-observation LL rows and the sample files of
     sample_posterior (the caller closes the engines whatever happens here).  rank_info: a
     rank of process_per_device -- this rank writes its chains' logLikelihood files, rank 0
@@ -524,6 +568,11 @@ def _sample_loop(engines, nIter, burn, thin, names, G, partial, saveLogLikelihoo
         rank_result = engines[0][0].rank_diagnostics(header)
         if write_files:
             _rankdiag.write_csv(rank_result, waic_dir)
+    group_result = None
+    if compute_group:
+        group_result = _group_of(engines, rank_info, n_real, names)
+        if group_result is not None and write_files:
+            _groupcmp.write_csvs(group_result, waic_dir)
     summary_result = None
     if compute_summary:
         summary_result = _summary_of(engines, rank_info, n_real, header)
@@ -568,6 +617,8 @@ def _sample_loop(engines, nIter, burn, thin, names, G, partial, saveLogLikelihoo
             res["convergence"] = conv_result
         if rank_result is not None:
             res["rank_diagnostics"] = rank_result
+        if group_result is not None:
+            res["group_comparison"] = group_result
         if summary_result is not None:
             res["summary"] = summary_result
             if conv_result is not None:

@@ -25,7 +25,8 @@ def samplePosterior(nChains, nIter, nSamples,
                     startWithMLE=False, startingPointValueRange=None,
                     nProcesses=1, displayProgress=True, loggingLevel="info",
                     computeWaic=False, computeDiagnostics=False, computeSummary=False,
-                    computeLoo=False, computeRankDiagnostics=False, **gpu_options):
+                    computeLoo=False, computeRankDiagnostics=False,
+                    computeGroupComparison=False, **gpu_options):
     """Sample the posterior of a nested model; samples go to outputDirectory/sample/.
 
     Arguments mirror the reference (posteriorSampling.py:28-145).  Keyword-only
@@ -41,8 +42,10 @@ def samplePosterior(nChains, nIter, nSamples,
     nestmc.loo) -- one engine only.  computeRankDiagnostics=True also computes the
     rank-normalised and folded split-R-hat, bulk-ESS and tail-ESS of every column on the GPU
     (rank_diagnostics.csv; nestmc.rankdiag) -- an even number of recorded rows and one engine
-    only.  Returns None like the reference unless
-    return_samples=True.
+    only.  computeGroupComparison=True also counts, per parameter, every group's rank among the
+    groups and every pair's wins on the GPU (group_ranking.csv, group_pairwise.csv;
+    nestmc.groupcmp) -- at least two groups, any number of engines.  Returns None like the
+    reference unless return_samples=True.
     """
     return sample_posterior(nChains, nIter, nSamples, parameterName, nGroups,
                             nResponsesPerGroup, pooling, logLikelihoodFunction,
@@ -53,4 +56,5 @@ def samplePosterior(nChains, nIter, nSamples,
                             loggingLevel=loggingLevel, computeWaic=computeWaic,
                             computeDiagnostics=computeDiagnostics,
                             computeSummary=computeSummary, computeLoo=computeLoo,
-                            computeRankDiagnostics=computeRankDiagnostics, **gpu_options)
+                            computeRankDiagnostics=computeRankDiagnostics,
+                            computeGroupComparison=computeGroupComparison, **gpu_options)
