@@ -338,6 +338,34 @@ int nmc_group_order(nmc_ctx* ctx, int row_begin, int n_rows, int n_valid, uint32
  * cols = P * (G + 2 * partial), partial 0 or 1, copied to `device`; needs no context.   */
 int nmc_group_order_of(int device, const double* x, int rows, int P, int G, int partial, int C,
                        int n_valid, uint32_t* hist, uint32_t* wins, int64_t* nonfinite);
+/* Posterior comoments of all store columns -- what the covariance and correlation matrix of
+ * the joint posterior are made of (the definitions are nestmc/correlation.py's docstring) --
+ * over recorded rows [row_begin, row_begin + n_rows) and local chains [0, n_valid), on the
+ * device from the sample store as it lies: the values are the recorded ones of
+ * posteriorSampling.py:640-659, 771-787; the reference only plots random pairs
+ * (sampleDiagnosis.py:690-725).  Samples s = (row, chain), S = n_rows * n_valid; columns k in
+ * header order:
+ *   mean[k]      = (sum_s x_k) / S, the sum in one fixed order (csrc/comoment.h)
+ *   minmax[0][k] = min_s x_k, minmax[1][k] = max_s x_k      (fp64 comparison)
+ *   nonfinite[k] = #{s : x_k is NaN or +-inf}       (callers treat a count as an error)
+ *   M[k][l]      = sum_s fl(x_k - mean[k]) fl(x_l - mean[l])
+ * in fp64 with fused multiply-adds (v_mfma_f64_16x16x4_f64) and no floating-point atomics:
+ * the partial tiles of the K-slices are added in slice order, so the bits depend on the
+ * window's values and on (n_rows, cols, C, n_valid) only -- not on where the window lies and
+ * not on what chains >= n_valid hold (they add exactly +0.0).  M[k][l] and M[l][k] are the
+ * same bits.  A constant column (min == max) has +0.0 in its row and column of M, the diagonal
+ * included; a column with a non-finite value has mean NaN and NaN in its row and column (also
+ * where it meets a constant one), and no other entry changes.  The call allocates and frees M
+ * and the partial tiles on the device (at most 1 GiB: cols <= 8192).  n_rows >= 1 and the rows
+ * inside the schedule's, 1 <= n_valid <= C, 2 <= S < 2^31, else -1 and nothing is written.
+ * Event slots 2 and 3 bracket the kernels.                                               */
+int nmc_comoments(nmc_ctx* ctx, int row_begin, int n_rows, int n_valid, double* mean,
+                  double* minmax /* [2][cols] */, double* M /* [cols][cols] */,
+                  int64_t* nonfinite);
+/* The same over a host array x[rows][cols][C] in the store's layout (all of its rows), copied
+ * to `device`; needs no context.                                                         */
+int nmc_comoments_of(int device, const double* x, int rows, int cols, int C, int n_valid,
+                     double* mean, double* minmax, double* M, int64_t* nonfinite);
 
 /* Timing on the context's stream (hipEvents). */
 int nmc_event_record(nmc_ctx* ctx, int slot);                 /* slot 0..15 */

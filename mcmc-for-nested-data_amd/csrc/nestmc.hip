@@ -30,6 +30,7 @@
 #include "psis.h"          // nmc_k_psis: PSIS-LOO over a sorted log-likelihood column
 #include "rankz.h"         // nmc_k_rank_transform: values to their ranks' normal scores
 #include "grouporder.h"    // nmc_k_group_order: the groups' rank histogram and pairwise wins
+#include "comoment.h"      // nmc_k_col_moments, nmc_k_comoment: the columns' centred Gram matrix
 
 #define NMC_VERSION "nestmc 0.2.0 (gfx950)"
 
@@ -2121,6 +2122,112 @@ int nmc_group_order_of(int device, const double* xs, int rows, int P, int G, int
                ? go_run(nullptr, st, dx, C, cols, P, G, pc, 0, rows, n_valid, hist, wins,
                         nonfinite)
                : fail(-2, std::string("group_order_of: ") + hipGetErrorString(e));
+  hipStreamSynchronize(st);
+  hipFree(dx);
+  hipStreamDestroy(st);
+  return rc;
+}
+
+// Posterior comoments of all store columns (comoment.h; nestmc/correlation.py has the
+// definitions; include/nestmc.h) -- no reference counterpart.  Three kernels over the store:
+// the column moments, the centred Gram's partial tiles per K-slice (MFMA), the slice sum.  M,
+// the scratch of the partial tiles and the moments are allocated and freed by the call.
+static int cm_check(int rows, int C, int cols, int row_begin, int n_rows, int n_valid) {
+  if (cols < 1) return fail(-1, "comoments: needs at least one column");
+  if (n_rows < 1 || row_begin < 0 || row_begin > rows - n_rows)
+    return fail(-1, "comoments: row range out of bounds");
+  if (n_valid < 1 || n_valid > C) return fail(-1, "n_valid must be in 1..n_chains");
+  if ((int64_t)n_rows * n_valid < 2) return fail(-1, "comoments: needs at least two samples");
+  if ((int64_t)n_rows * n_valid >= ((int64_t)1 << 31))
+    return fail(-1, "comoments: 2^31 or more samples");
+  // M and at least one slice of scratch within the 1 GiB the reductions allow themselves
+  if ((int64_t)cols * cols > ((int64_t)1 << 26))          // 2 cols^2 8 bytes > 2^30
+    return fail(-1, "comoments: the matrix and its scratch of " + std::to_string(cols) +
+                        " columns do not fit 1 GiB of device memory (8192 columns at most)");
+  return 0;
+}
+
+// x: the context whose event slots 2 / 3 bracket the kernels, or NULL.
+static int cm_run(nmc_ctx* x, hipStream_t st, const double* samples, int C, int cols,
+                  int row_begin, int n_rows, int n_valid, double* mean, double* minmax,
+                  double* M, int64_t* nonfinite) {
+  const size_t nm = (size_t)cols * cols;
+  const int64_t fit = (((int64_t)1 << 30) - (int64_t)nm * 8) / ((int64_t)nm * 8);
+  const int max_slices = (int)std::min<int64_t>(NMC_CM_MAX_SLICES, fit);   // (>= 1: cm_check)
+  const int rps = nmc_cm_slice_rows(n_rows, max_slices);
+  const int nslice = (n_rows + rps - 1) / rps;
+  const int nt = (cols + NMC_CM_TILE - 1) / NMC_CM_TILE;
+  const int npair = nt * (nt + 1) / 2;
+  double* o = nullptr;                    // M, scratch [nslice][cols][cols], mean, minmax
+  unsigned long long* d_bad = nullptr;
+  const size_t no = nm * (1 + (size_t)nslice) + 3 * (size_t)cols;
+  hipError_t e = hipMalloc(&o, no * 8);
+  if (e == hipSuccess) e = hipMalloc(&d_bad, (size_t)cols * 8);
+  double* d_M = o;
+  double* d_scr = o + nm;
+  double* d_mean = d_scr + nm * nslice;
+  double* d_mm = d_mean + cols;
+  int rc = 0;
+  if (e == hipSuccess && x) rc = nmc_event_record(x, 2);
+  if (e == hipSuccess && !rc) {
+    hipLaunchKernelGGL(nmc_k_col_moments, dim3((unsigned)cols), dim3(NMC_CM_THREADS), 0, st,
+                       samples, C, cols, row_begin, n_rows, n_valid, d_mean, d_mm, d_bad);
+    hipLaunchKernelGGL(nmc_k_comoment, dim3((unsigned)npair, (unsigned)nslice),
+                       dim3(NMC_CM_THREADS), 0, st, samples, C, cols, nt, row_begin, n_rows, rps,
+                       n_valid, d_mean, d_scr);
+    hipLaunchKernelGGL(nmc_k_comoment_sum,
+                       dim3((unsigned)((cols + NMC_CM_THREADS - 1) / NMC_CM_THREADS),
+                            (unsigned)cols),
+                       dim3(NMC_CM_THREADS), 0, st, d_scr, cols, nslice, d_mm, d_bad, d_M);
+    e = hipGetLastError();
+    if (e == hipSuccess && x) rc = nmc_event_record(x, 3);
+  }
+  // (staged: the caller's arrays are written only when everything before has succeeded)
+  std::vector<unsigned long long> bad(cols);
+  std::vector<double> mo(3 * (size_t)cols);
+  if (e == hipSuccess && !rc)
+    e = hipMemcpyAsync(bad.data(), d_bad, (size_t)cols * 8, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess && !rc)
+    e = hipMemcpyAsync(mo.data(), d_mean, 3 * (size_t)cols * 8, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess && !rc) e = hipStreamSynchronize(st);
+  if (e == hipSuccess && !rc) e = hipMemcpy(M, d_M, nm * 8, hipMemcpyDeviceToHost);
+  if (e != hipSuccess) rc = fail(-2, std::string("comoments: ") + hipGetErrorString(e));
+  if (!rc) {
+    for (int k = 0; k < cols; ++k) nonfinite[k] = (int64_t)bad[k];
+    std::copy(mo.begin(), mo.begin() + cols, mean);
+    std::copy(mo.begin() + cols, mo.end(), minmax);
+  }
+  hipStreamSynchronize(st);
+  hipFree(o); hipFree(d_bad);
+  return rc;
+}
+
+int nmc_comoments(nmc_ctx* x, int row_begin, int n_rows, int n_valid, double* mean,
+                  double* minmax, double* M, int64_t* nonfinite) {
+  RES_PARK(x);
+  hipSetDevice(x->device);
+  const Dev& d = x->d;
+  if (int rc = cm_check(d.n_rows, x->C, d.cols, row_begin, n_rows, n_valid)) return rc;
+  HIPCHK(hipStreamSynchronize(x->stream));
+  if (int rc = check_timeout(x)) return rc;
+  return cm_run(x, x->stream, d.samples, x->C, d.cols, row_begin, n_rows, n_valid, mean, minmax,
+                M, nonfinite);
+}
+
+int nmc_comoments_of(int device, const double* xs, int rows, int cols, int C, int n_valid,
+                     double* mean, double* minmax, double* M, int64_t* nonfinite) {
+  if (rows < 1 || C < 1) return fail(-1, "comoments_of: need rows >= 1 and C >= 1");
+  if (int rc = cm_check(rows, C, cols, 0, rows, n_valid)) return rc;
+  HIPCHK(hipSetDevice(device));
+  hipStream_t st;
+  HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+  double* dx = nullptr;
+  const size_t nx = (size_t)rows * cols * C;
+  hipError_t e = hipMalloc(&dx, nx * 8);
+  if (e == hipSuccess) e = hipMemcpyAsync(dx, xs, nx * 8, hipMemcpyHostToDevice, st);
+  int rc = e == hipSuccess
+               ? cm_run(nullptr, st, dx, C, cols, 0, rows, n_valid, mean, minmax, M, nonfinite)
+               : fail(-2, std::string("comoments_of: ") + hipGetErrorString(e));
   hipStreamSynchronize(st);
   hipFree(dx);
   hipStreamDestroy(st);

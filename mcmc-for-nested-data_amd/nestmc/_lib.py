@@ -94,6 +94,11 @@ SIGNATURES = {
     "nmc_group_order_of": (ctypes.c_int, [ctypes.c_int, _c_double_p, ctypes.c_int, ctypes.c_int,
                                           ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                           ctypes.c_int, _c_uint32_p, _c_uint32_p, _c_int64_p]),
+    "nmc_comoments": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                     _c_double_p, _c_double_p, _c_double_p, _c_int64_p]),
+    "nmc_comoments_of": (ctypes.c_int, [ctypes.c_int, _c_double_p, ctypes.c_int, ctypes.c_int,
+                                        ctypes.c_int, ctypes.c_int, _c_double_p, _c_double_p,
+                                        _c_double_p, _c_int64_p]),
     "nmc_event_record":(ctypes.c_int, [_vp, ctypes.c_int]),
     "nmc_event_elapsed": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int,
                                          ctypes.POINTER(ctypes.c_float)]),

@@ -426,6 +426,39 @@ class Engine:
                                    % self.group_nonfinite)
         return _groupcmp.finish(raw["hist"], raw["wins"], raw["n_samples"], names)
 
+    def comoments(self, row_begin=0, n_rows=None, n_valid=None):
+        """The columns' moments and centred comoments over recorded rows [row_begin, row_begin
+        + n_rows) and local chains [0, n_valid), on the device from the sample store
+        (nmc_comoments; nestmc.correlation has the definitions): a dict of mean, min, max
+        [cols], M [cols, cols], nonfinite [cols] (int64) and n_samples."""
+        if n_rows is None:
+            n_rows = self.n_rows - row_begin
+        if n_valid is None:
+            n_valid = self.C
+        n_rows, n_valid = int(n_rows), int(n_valid)
+        cols = self.cols
+        mean = numpy.empty(cols)
+        minmax = numpy.empty((2, cols))
+        M = numpy.empty((cols, cols))
+        bad = numpy.empty(cols, dtype=numpy.int64)
+        check(self.lib.nmc_comoments(self.h, int(row_begin), n_rows, n_valid, _lib.dptr(mean),
+                                     _lib.dptr(minmax), _lib.dptr(M),
+                                     bad.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
+        return dict(mean=mean, min=minmax[0].copy(), max=minmax[1].copy(), M=M, nonfinite=bad,
+                    n_samples=n_rows * n_valid)
+
+    def correlation(self, names=None, row_begin=0, n_rows=None, n_valid=None):
+        """The CorrelationResult (nestmc.correlation: mean, sd, covariance and correlation
+        matrix of all columns) of this engine's chains over the given rows.  names: the
+        columns' names (default "c<k>").  A value that is not finite is an error."""
+        from . import correlation as _correlation
+        raw = self.comoments(row_begin, n_rows, n_valid)
+        self.correlation_nonfinite = int(raw["nonfinite"].sum())
+        if self.correlation_nonfinite:
+            raise _lib.NestmcError("correlation: %d values were not finite"
+                                   % self.correlation_nonfinite)
+        return _correlation.finish(raw, names)
+
     def eval_obs_ll(self):
         """Per-observation LL at the current state: [C, n_obs]."""
         out = numpy.empty((self.C, int(self.off[-1])))

@@ -24,6 +24,7 @@ import numpy
 from . import _lib
 from . import output
 from . import convergence as _conv
+from . import correlation as _correlation
 from . import groupcmp as _groupcmp
 from . import summary as _summary
 from . import loo as _loo
@@ -69,7 +70,7 @@ def sample_posterior(nChains, nIter, nSamples, parameterName, nGroups, nResponse
                      write_files=True, replay=None, process_per_device=False, _rank=None,
                      computeWaic=False, computeDiagnostics=False, computeSummary=False,
                      computeLoo=False, computeRankDiagnostics=False,
-                     computeGroupComparison=False):
+                     computeGroupComparison=False, computeCorrelation=False):
     """Drop-in for posteriorSampling.samplePosterior (same positional/keyword API).
 
     Extra keyword-only options (all optional):
@@ -140,6 +141,18 @@ def sample_posterior(nChains, nIter, nSamples, parameterName, nGroups, nResponse
                  caller and the ranks of process_per_device give the one engine's numbers bit
                  for bit.  pooling="complete" has one group and raises ValueError before
                  sampling starts
+      computeCorrelation  after the loop, compute on the GPU from the device sample store the
+                 posterior covariance and correlation matrix of all columns over all recorded
+                 rows and chains (nestmc.correlation: the comoments by fp64 matrix
+                 instructions, only [cols, cols] leaves the device):
+                 outputDirectory/correlation.csv (the square correlation matrix),
+                 correlation_pairs.csv (the pairs a person reads first: the parameters of a
+                 group against each other and, under partial pooling, every theta_g against
+                 its _mu and _sigma2) and "correlation" (a nestmc.correlation
+                 .CorrelationResult) in the returned dict.  Several engines and the ranks of
+                 process_per_device are merged by Chan's update: within rounding of the one
+                 engine's numbers, not bit-identical.  Fewer than two samples raise ValueError
+                 before sampling starts
     nProcesses sizes the host threads used for chain initialisation and CSV writing.
     """
     start_time = datetime.datetime.now()
@@ -218,6 +231,12 @@ def sample_posterior(nChains, nIter, nSamples, parameterName, nGroups, nResponse
                              "recorded rows of all chains give %d" % n_val)
     if computeLoo and len(record_iterations(nIter, burn, thin)) * nChains < 2:
         raise ValueError("computeLoo needs at least two samples")
+    if computeCorrelation:
+        n_val = len(record_iterations(nIter, burn, thin)) * \
+            (nChains if chains is None else len(chains))
+        if n_val < 2:
+            raise ValueError("computeCorrelation needs at least two samples: the recorded rows "
+                             "of all chains give %d" % n_val)
     sizes = _sizes(nGroups, nResponsesPerGroup, pooling)
     G = len(sizes)
     priors = None
@@ -254,7 +273,8 @@ def sample_posterior(nChains, nIter, nSamples, parameterName, nGroups, nResponse
                   return_samples=return_samples, write_files=write_files,
                   computeWaic=computeWaic, computeDiagnostics=computeDiagnostics,
                   computeSummary=computeSummary,
-                  computeGroupComparison=computeGroupComparison)
+                  computeGroupComparison=computeGroupComparison,
+                  computeCorrelation=computeCorrelation)
         res = ranks.run_per_device(kw, devices)
         _finish_log(logger, [], start_time, displayProgress)
         return res
@@ -336,7 +356,8 @@ def sample_posterior(nChains, nIter, nSamples, parameterName, nGroups, nResponse
                             n_real=nChains, compute_conv=bool(computeDiagnostics),
                             compute_summary=bool(computeSummary), compute_loo=bool(computeLoo),
                             compute_rank=bool(computeRankDiagnostics),
-                            compute_group=bool(computeGroupComparison))
+                            compute_group=bool(computeGroupComparison),
+                            compute_corr=bool(computeCorrelation))
     finally:
         for eng, _, _ in engines:
             eng.close()
@@ -468,6 +489,31 @@ def _group_of(engines, rank_info, n_real, names):
     return _groupcmp.finish(part["hist"], part["wins"], part["n_samples"], names)
 
 
+def _correlation_of(engines, rank_info, n_real, header):
+    """computeCorrelation: every engine's moments and comoments over all recorded rows and its
+    real chains (padding chains, ids >= n_real, excluded through n_valid; an engine with none
+    adds the identity), merged in engine order by Chan's update; the ranks of
+    process_per_device send theirs as bytes over the host group and rank 0 merges them in rank
+    order and finishes (the other ranks: None).  A value that is not finite is an error."""
+    cols = engines[0][0].cols
+    parts = []
+    for eng, _, ids in engines:
+        n_valid = sum(1 for c in ids if c < n_real)
+        parts.append(eng.comoments(n_valid=n_valid) if n_valid > 0
+                     else _correlation.identity(cols))
+    part = _correlation.merge(parts)
+    if rank_info is not None:
+        got = rank_info["hg"].gather(numpy.ascontiguousarray(_correlation.pack(part)).tobytes())
+        if rank_info["rank"] != 0:
+            return None
+        part = _correlation.merge([_correlation.unpack(numpy.frombuffer(b, dtype=numpy.float64),
+                                                       cols) for b in got])
+    bad = int(part["nonfinite"].sum())
+    if bad:
+        raise _lib.NestmcError("correlation: %d values were not finite" % bad)
+    return _correlation.finish(part, header)
+
+
 def _summary_of(engines, rank_info, n_real, header):
     """computeSummary: one engine sorts its store's columns and only per-column results leave
     the device.  Several engines, and the ranks of process_per_device, each sort the values of
@@ -502,7 +548,7 @@ def _sample_loop(engines, nIter, burn, thin, names, G, partial, saveLogLikelihoo
                  sample_dir, threads, displayProgress, return_samples, logger, chain_logs,
                  start_time, rank_info=None, compute_waic=False, waic_dir=None,
                  n_real=None, compute_conv=False, compute_summary=False, compute_loo=False,
-                 compute_rank=False, compute_group=False):
+                 compute_rank=False, compute_group=False, compute_corr=False):
     """The device loop, the per-observation LL rows and the sample files of
     sample_posterior (the caller closes the engines whatever happens here).  rank_info: a
     rank of process_per_device -- this rank writes its chains' logLikelihood files, rank 0
@@ -573,6 +619,11 @@ def _sample_loop(engines, nIter, burn, thin, names, G, partial, saveLogLikelihoo
         group_result = _group_of(engines, rank_info, n_real, names)
         if group_result is not None and write_files:
             _groupcmp.write_csvs(group_result, waic_dir)
+    corr_result = None
+    if compute_corr:
+        corr_result = _correlation_of(engines, rank_info, n_real, header)
+        if corr_result is not None and write_files:
+            _correlation.write_csvs(corr_result, waic_dir, len(names), G, partial)
     summary_result = None
     if compute_summary:
         summary_result = _summary_of(engines, rank_info, n_real, header)
@@ -619,6 +670,8 @@ def _sample_loop(engines, nIter, burn, thin, names, G, partial, saveLogLikelihoo
             res["rank_diagnostics"] = rank_result
         if group_result is not None:
             res["group_comparison"] = group_result
+        if corr_result is not None:
+            res["correlation"] = corr_result
         if summary_result is not None:
             res["summary"] = summary_result
             if conv_result is not None:

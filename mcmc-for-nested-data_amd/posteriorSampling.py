@@ -26,7 +26,7 @@ def samplePosterior(nChains, nIter, nSamples,
                     nProcesses=1, displayProgress=True, loggingLevel="info",
                     computeWaic=False, computeDiagnostics=False, computeSummary=False,
                     computeLoo=False, computeRankDiagnostics=False,
-                    computeGroupComparison=False, **gpu_options):
+                    computeGroupComparison=False, computeCorrelation=False, **gpu_options):
     """Sample the posterior of a nested model; samples go to outputDirectory/sample/.
 
     Arguments mirror the reference (posteriorSampling.py:28-145).  Keyword-only
@@ -44,8 +44,10 @@ def samplePosterior(nChains, nIter, nSamples,
     (rank_diagnostics.csv; nestmc.rankdiag) -- an even number of recorded rows and one engine
     only.  computeGroupComparison=True also counts, per parameter, every group's rank among the
     groups and every pair's wins on the GPU (group_ranking.csv, group_pairwise.csv;
-    nestmc.groupcmp) -- at least two groups, any number of engines.  Returns None like the
-    reference unless return_samples=True.
+    nestmc.groupcmp) -- at least two groups, any number of engines.  computeCorrelation=True
+    also computes the posterior covariance and correlation matrix of all columns on the GPU
+    (correlation.csv, correlation_pairs.csv; nestmc.correlation) -- at least two samples, any
+    number of engines.  Returns None like the reference unless return_samples=True.
     """
     return sample_posterior(nChains, nIter, nSamples, parameterName, nGroups,
                             nResponsesPerGroup, pooling, logLikelihoodFunction,
@@ -57,4 +59,5 @@ def samplePosterior(nChains, nIter, nSamples,
                             computeDiagnostics=computeDiagnostics,
                             computeSummary=computeSummary, computeLoo=computeLoo,
                             computeRankDiagnostics=computeRankDiagnostics,
-                            computeGroupComparison=computeGroupComparison, **gpu_options)
+                            computeGroupComparison=computeGroupComparison,
+                            computeCorrelation=computeCorrelation, **gpu_options)
