@@ -216,6 +216,37 @@ int nmc_write_ll_csvs(nmc_ctx* ctx, const char* dir, const int32_t* chain_ids, i
  * Event slots 14 and 15 bracket the kernel.                                      */
 int nmc_waic_partials(nmc_ctx* ctx, int row_begin, int n_rows, int n_valid, double* part,
                       int64_t* nonfinite);
+/* Posterior predictive checks (csrc/ppc.h; no counterpart in the reference).  A replicate
+ * y_rep of response field j of observation i at the values of recorded row r and chain c is
+ * the family's predict() on the Philox block with counter (r, i, j, purpose 4) and key
+ * (chain_base + c, seed): it depends on nothing else.  *nresp: the family's response fields
+ * (linreg, logistic: 1, the last field; gauss_mean: every field; a user family: 1 if its
+ * source defines nmc_user_predict and NMC_USER_RESP, else 0).  A family with 0, or 2^32 or
+ * more observations, is refused (-1) by the two calls below.
+ * nmc_ppc_draws: out[C][n_rows][n_obs][nresp], the replicates themselves (at most 65535 rows
+ * per call, as nmc_obs_ll_rows).
+ * nmc_ppc_partials: over recorded rows [row_begin, row_begin + n_rows) and local chains
+ * [0, n_valid), per chain block (CB = ceil(C / 64)):
+ *   obs_state[CB][3][nresp][n_obs]      n, Welford's mean and M2 of y_rep over the samples
+ *   obs_count[CB][2][nresp][n_obs]      lt = #{y_rep < y}, eq = #{y_rep == y}
+ *   group_state[CB][G][nresp][4][3]     n, mean, M2 of T(y_rep) over the samples, T = the
+ *                                       group's mean, population variance, minimum, maximum of
+ *                                       its observations taken in order
+ *   group_count[CB][G][nresp][4][2]     gt = #{T(y_rep) > T(y)}, eq = #{T(y_rep) == T(y)}
+ *   ty[G][nresp][4]                     T(y), by the same device function
+ * the 64 chains of a block (and, for the groups, waves and row slices) merged in the fixed
+ * order csrc/ppc.h documents; nestmc/ppc.py merges the blocks and finishes.  Chains >= n_valid
+ * enter as the identity (zero states and counts).  The counts are uint32: a block's count is
+ * at most 64 n_rows, so n_rows < 2^26; callers add blocks in int64.  Other argument errors as
+ * nmc_waic_partials.  *nonfinite: the draws that were not finite, each counted once; they
+ * enter the states as NaN and no count (callers treat a count as an error).  Event slots 13,
+ * 14 and 15: the observation kernel runs between 13 and 14, the group kernels between 14
+ * and 15.                                                                         */
+int nmc_ppc_nresp(nmc_ctx* ctx, int* nresp);
+int nmc_ppc_draws(nmc_ctx* ctx, int row_begin, int n_rows, double* out);
+int nmc_ppc_partials(nmc_ctx* ctx, int row_begin, int n_rows, int n_valid, double* obs_state,
+                     uint32_t* obs_count, double* group_state, uint32_t* group_count, double* ty,
+                     int64_t* nonfinite);
 /* The convergence diagnostic's partial sums (Diagnostic, sampleDiagnosis.py:136-255: the split
  * of every chain into two halves :136-155, the means and variances of :158-187, the variogram
  * of :189-194) over recorded rows [row_begin, row_begin + n_rows) and local chains
@@ -450,7 +481,8 @@ int nmc_debug_softplus(const double* x, int n, double* out, int on_device);
 /* The inverse of nmc_get_samples: writes recorded rows [row_begin, row_begin+n_rows) of the
  * device sample store from in[row][col][C] (the store as set_schedule sized it; no sampling
  * needed), so that the store's consumers -- nmc_obs_ll_rows, nmc_write_ll_csvs,
- * nmc_waic_partials, nmc_loo, nmc_conv_partials, nmc_summary, nmc_rank_partials -- can be run
+ * nmc_waic_partials, nmc_ppc_partials, nmc_loo, nmc_conv_partials, nmc_summary,
+ * nmc_rank_partials -- can be run
  * on rows a sampler would not produce.  Nothing in the product path calls it.           */
 int nmc_debug_set_samples(nmc_ctx* ctx, int row_begin, int n_rows, const double* in);
 /* Diagnostic build only (make stamps -> libnestmc_stamps.so): shader-clock phase

@@ -96,6 +96,7 @@ struct nmc_ctx {
   nmc_waic_tile* wtiles = nullptr;        // [n_wtiles] observation tiles of nmc_k_waic (waic.h)
   int n_wtiles = 0;
   unsigned long long* wbad = nullptr;     // non-finite terms nmc_k_waic met (zeroed per call)
+  int nresp = 0;                          // response fields the family can draw (ppc.h; 0: none)
   int split_batch = 0;                    // row split: chain blocks per (resident) launch
   int sweep_batch = 0;                    // nmc_k_sweep with Dev.gsep: chain blocks per launch
   unsigned gepoch = 0;                    // Dev.gsep launches so far (Dev.gep)
@@ -274,7 +275,12 @@ enum {
   NMC_OP_CAPACITY = 5,     // result = resident step-kernel workgroups on the device
   NMC_OP_RES_OK = 6,       // result = 1: the run mode has a resident instance, grid co-resident
   NMC_OP_WAIC = 7,         // sample rows [i0, i1), chains < nc valid -> out = [CB][5][n_obs] (waic.h)
-  NMC_OP_LOO_LL = 8        // sample rows [i0, i1), observations [o0, o0 + nb) -> out = [i1 - i0][nb][C]
+  NMC_OP_LOO_LL = 8,       // sample rows [i0, i1), observations [o0, o0 + nb) -> out = [i1 - i0][nb][C]
+  NMC_OP_PPC_DRAWS = 9,    // sample rows [i0, i1) -> out = [C][i1 - i0][n_obs][NRESP] (ppc.h)
+  NMC_OP_PPC_OBS = 10,     // sample rows [i0, i1), chains < nc valid -> out = [CB][3][NRESP][n_obs],
+                           // cnt = [CB][2][NRESP][n_obs]
+  NMC_OP_PPC_GROUP = 11    // the same rows and chains in nb slices -> out = [nb][CB][G][NRESP][4][3],
+                           // cnt = [nb][CB][G][NRESP][4][2], aux = T(y) [G][NRESP][4]
 };
 struct NmcCall {
   int op = 0;
@@ -287,6 +293,7 @@ struct NmcCall {
   const double* in = nullptr;
   double* out = nullptr;
   double* aux = nullptr;   // op-specific device scratch
+  uint32_t* cnt = nullptr; // NMC_OP_PPC_*: the integer counts
   int result = 0;
   int result2 = 0;         // NMC_OP_RES_OK: the resident instance's VGPRs per lane
 };

@@ -123,6 +123,34 @@ static int nmc_fam_call(nmc_ctx* x, const Fam& fam, NmcCall& c) {
       HIPCHK(hipGetLastError());
       return 0;
     }
+    case NMC_OP_PPC_DRAWS: {
+      const int n = c.i1 - c.i0;
+      if (n <= 0 || x->n_obs == 0) return 0;
+      const dim3 grid((unsigned)((x->n_obs + 255) / 256), (unsigned)x->C, (unsigned)n);
+      hipLaunchKernelGGL(nmc_k_ppc_draws<Fam>, grid, dim3(256), 0, x->stream, x->d, fam,
+                         (const int*)x->gidx, x->n_obs, x->pooling == NMC_POOL_PARTIAL ? 2 : 0,
+                         c.i0, n, c.out);
+      HIPCHK(hipGetLastError());
+      return 0;
+    }
+    case NMC_OP_PPC_OBS: {
+      if (x->n_wtiles == 0) return 0;
+      const dim3 grid((unsigned)((x->n_wtiles + 3) / 4), (unsigned)x->d.CB);
+      hipLaunchKernelGGL(nmc_k_ppc_obs<Fam>, grid, dim3(256), 0, x->stream, x->d, fam, x->d.obs,
+                         (const nmc_waic_tile*)x->wtiles, x->n_wtiles, x->n_obs,
+                         x->pooling == NMC_POOL_PARTIAL ? 2 : 0, c.i0, c.i1 - c.i0, c.nc, c.out,
+                         c.cnt, x->wbad);
+      HIPCHK(hipGetLastError());
+      return 0;
+    }
+    case NMC_OP_PPC_GROUP: {
+      const dim3 grid((unsigned)(x->G * Fam::NRESP), (unsigned)x->d.CB, (unsigned)c.nb);
+      hipLaunchKernelGGL(nmc_k_ppc_group<Fam>, grid, dim3(256), 0, x->stream, x->d, fam, x->d.obs,
+                         x->pooling == NMC_POOL_PARTIAL ? 2 : 0, c.i0, c.i1 - c.i0, c.nc, c.out,
+                         c.cnt, c.aux);
+      HIPCHK(hipGetLastError());
+      return 0;
+    }
     case NMC_OP_LOO_LL: {
       const int n = c.i1 - c.i0;
       if (n <= 0 || c.nb <= 0) return 0;

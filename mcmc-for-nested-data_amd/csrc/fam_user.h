@@ -13,6 +13,15 @@
 // sum of the per-observation values in the kernels' fixed order, the same order as every
 // built-in family, so a user functor that restates a built-in family's expression (e.g.
 // FamLogistic's fma chain) reproduces it bit for bit.
+//
+// A source that also defines
+//   __device__ double nmc_user_predict(const double* theta, const double* row, const double* k,
+//                                      double ua, double ub, double z);
+// and NMC_USER_RESP (the response's field; nestmc.DeviceLikelihood(response_field=) puts the
+// define in front of the source) can draw posterior predictive replicates of row[NMC_USER_RESP]
+// (ppc.h): ua, ub are the draw's two uniforms in [0, 1), z their Box-Muller normal.  With
+// NMC_USER_RESP_INT defined too (DeviceLikelihood(response_integer=True)) the response takes
+// integer values -- counts, 0 / 1 -- and the groups' statistics come from exact sums.
 #pragma once
 
 struct FamUser {
@@ -52,4 +61,20 @@ struct FamUser {
   __device__ __forceinline__ double obs_ll(const Reg& r, const double* __restrict__ row) const {
     return nmc_user_loglik(r.t, row, k);
   }
+#ifdef NMC_USER_RESP
+  static constexpr int NRESP = 1;
+#ifdef NMC_USER_RESP_INT
+  static constexpr bool RESP_INT = true;
+#else
+  static constexpr bool RESP_INT = false;
+#endif
+  __device__ __forceinline__ static int resp_field(int) { return NMC_USER_RESP; }
+  __device__ __forceinline__ double predict(const Reg& r, const double* __restrict__ row, int,
+                                            double ua, double ub, double z) const {
+    return nmc_user_predict(r.t, row, k, ua, ub, z);
+  }
+#else
+  static constexpr int NRESP = 0;   // no nmc_user_predict: the host refuses the ppc calls
+  static constexpr bool RESP_INT = false;
+#endif
 };

@@ -12,6 +12,11 @@
 //            (StepMethod.logLikelihood rows, posteriorSampling.py:656-659)
 //   gconst()/finish_fast() the same group LL with the per-group constant hoisted
 //            out of the decision's critical path (<= 1 ulp from finish())
+//   NRESP, resp_field(j), predict()  the posterior predictive draw (ppc.h): the family has
+//            NRESP response fields (0: it cannot draw), response j is row[resp_field(j)], and
+//            predict(reg, row, j, ua, ub, z) is one replicate of it from the Philox block's
+//            two uniforms and their Box-Muller normal z; RESP_INT: the response takes integer
+//            values (a group's mean and variance then come from exact sums, ppc.h)
 // Algebra is restructured (e.g. sum r^2 then scale once) but no fast-math: NaN and
 // inf propagate exactly as the reference's MH branches (:347-367) need.
 #pragma once
@@ -124,6 +129,20 @@ struct FamLinreg {
     const double ls = sigma_known > 0.0 ? log_sigma_known : log(s);
     return (-(t * t) / 2.0 - NMC_LOG_C) - ls;
   }
+  // y_rep = yhat + sigma z, yhat the unfused sum of obs_ll; NaN unless sigma > 0
+  static constexpr int NRESP = 1;
+  static constexpr bool RESP_INT = false;
+  __device__ __forceinline__ static int resp_field(int) { return K; }
+  __device__ __forceinline__ double predict(const Reg& r, const double* __restrict__ row, int,
+                                            double, double, double z) const {
+    double yh = 0.0;
+    if (intercept) yh = r.b0;
+#pragma unroll
+    for (int j = 0; j < K; ++j) yh = yh + row[j] * r.b[j];
+    const double s = r.sig;
+    if (!(s > 0.0)) return nmc_nan();
+    return yh + s * z;
+  }
 };
 
 // ---------------------------------------------------------------------------
@@ -203,6 +222,22 @@ struct FamGaussMean {
     for (int j = 0; j < NF; ++j) out = out + nmc_norm_logpdf(r.t[j], row[j], sd[j], lsd[j]);
     return out;
   }
+  // the density is symmetric in theta_j and m_ij: the replicate of the recorded mean is
+  // t_j + sd_j z, NaN unless sd_j > 0 (j selects by compares: no indexed register array)
+  static constexpr int NRESP = NF;
+  static constexpr bool RESP_INT = false;
+  __device__ __forceinline__ static int resp_field(int j) { return j; }
+  __device__ __forceinline__ double predict(const Reg& r, const double* __restrict__, int j,
+                                            double, double, double z) const {
+    double t = r.t[0], s = sd[0];
+#pragma unroll
+    for (int q = 1; q < NF; ++q) {
+      t = j == q ? r.t[q] : t;
+      s = j == q ? sd[q] : s;
+    }
+    if (!(s > 0.0)) return nmc_nan();
+    return t + s * z;
+  }
 };
 
 // ---------------------------------------------------------------------------
@@ -263,5 +298,19 @@ struct FamLogistic {
 #pragma unroll
     for (int j = 0; j < K; ++j) eta = eta + row[j] * r.b[j];
     return row[K] * eta - logaddexp0(eta);
+  }
+  // y_rep = 1 if ua < p, p = 1 / (1 + exp(-eta)), eta the unfused sum of obs_ll; NaN eta -> NaN
+  static constexpr int NRESP = 1;
+  static constexpr bool RESP_INT = true;    // 0 / 1
+  __device__ __forceinline__ static int resp_field(int) { return K; }
+  __device__ __forceinline__ double predict(const Reg& r, const double* __restrict__ row, int,
+                                            double ua, double, double) const {
+    double eta = 0.0;
+    if (intercept) eta = r.b0;
+#pragma unroll
+    for (int j = 0; j < K; ++j) eta = eta + row[j] * r.b[j];
+    if (eta != eta) return eta;
+    const double p = 1.0 / (1.0 + exp(-eta));
+    return ua < p ? 1.0 : 0.0;
   }
 };

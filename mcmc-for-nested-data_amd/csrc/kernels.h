@@ -45,3 +45,4 @@
 #include "step.h"        // nmc_k_run, tuning, the step variates
 #include "ll_kernels.h"  // group and per-observation log-likelihood kernels
 #include "waic.h"        // WAIC: per-observation reduction over the sample store
+#include "ppc.h"         // posterior predictive draws and their reductions over the store

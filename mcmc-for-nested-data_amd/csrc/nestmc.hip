@@ -653,6 +653,7 @@ static int create_on_device(nmc_ctx* x, const int64_t* group_offsets, const doub
       x->ncu = prop.multiProcessorCount;
   }
   x->nacc = ll_family == NMC_LL_GAUSS_MEAN ? n_fields : 1;
+  x->nresp = ll_family == NMC_LL_GAUSS_MEAN ? n_fields : 1;   // (families.h NRESP; user: attach)
   if (ll_family >= NMC_LL_USER_BASE) {   // runtime-compiled family: module + constants
     if (int rc0 = nmc_user_attach(x, ll_family)) return rc0;
     if (n_ll_consts > 0) {
@@ -1677,6 +1678,147 @@ int nmc_waic_partials(nmc_ctx* x, int row_begin, int n_rows, int n_valid, double
     if (e != hipSuccess) rc = fail(-2, std::string("waic_partials: ") + hipGetErrorString(e));
     *nonfinite = (int64_t)bad;
   }
+  hipFree(o);
+  return rc;
+}
+
+// ---------------------------------------------------------------------------
+// Posterior predictive checks (ppc.h; include/nestmc.h)
+// ---------------------------------------------------------------------------
+// nmc_k_ppc_group's slices merged in the order 0 .. NS - 1, A the merged so far: one thread
+// per (chain block, group, field, statistic).
+__global__ void __launch_bounds__(256)
+nmc_k_ppc_group_fin(const double* __restrict__ gs, const uint32_t* __restrict__ gc, int NS, int n,
+                    double* __restrict__ os, uint32_t* __restrict__ oc) {
+  const int t = (int)blockIdx.x * 256 + threadIdx.x;
+  if (t >= n) return;
+  nmc_ppc_state a = {gs[(size_t)t * 3], gs[(size_t)t * 3 + 1], gs[(size_t)t * 3 + 2]};
+  uint32_t c0 = gc[(size_t)t * 2], c1 = gc[(size_t)t * 2 + 1];
+  for (int s = 1; s < NS; ++s) {
+    const size_t at = (size_t)s * n + t;
+    const nmc_ppc_state b = {gs[at * 3], gs[at * 3 + 1], gs[at * 3 + 2]};
+    a = nmc_ppc_merge(a, b);
+    c0 += gc[at * 2];
+    c1 += gc[at * 2 + 1];
+  }
+  os[(size_t)t * 3] = a.n; os[(size_t)t * 3 + 1] = a.mean; os[(size_t)t * 3 + 2] = a.M2;
+  oc[(size_t)t * 2] = c0; oc[(size_t)t * 2 + 1] = c1;
+}
+
+static int ppc_check(nmc_ctx* x) {
+  if (x->nresp < 1)
+    return fail(-1, "this family cannot draw from its likelihood: a user family's source must "
+                    "define nmc_user_predict and NMC_USER_RESP (DeviceLikelihood(response_field=))");
+  if (x->n_obs >= ((int64_t)1 << 32))
+    return fail(-1, "posterior predictive draws: 2^32 or more observations");
+  return 0;
+}
+
+int nmc_ppc_nresp(nmc_ctx* x, int* nresp) {
+  *nresp = x->nresp;
+  return 0;
+}
+
+int nmc_ppc_draws(nmc_ctx* x, int row_begin, int n_rows, double* out) {
+  RES_PARK(x);
+  hipSetDevice(x->device);
+  if (row_begin < 0 || n_rows < 0 || row_begin > x->d.n_rows - n_rows || n_rows > 65535)
+    return fail(-1, "row range out of bounds (at most 65535 rows per call)");
+  if (x->C > 65535) return fail(-1, "ppc_draws: at most 65535 chains per engine");
+  if (int rc = ppc_check(x)) return rc;
+  HIPCHK(hipStreamSynchronize(x->stream));
+  if (int rc = check_timeout(x)) return rc;
+  if (int rc = ensure_gidx(x)) return rc;
+  const size_t n = (size_t)x->C * n_rows * x->n_obs * x->nresp;
+  if (n == 0) return 0;
+  double* o = nullptr;
+  HIPCHK(hipMalloc(&o, n * 8));
+  NmcCall c;
+  c.op = NMC_OP_PPC_DRAWS;
+  c.i0 = row_begin;
+  c.i1 = row_begin + n_rows;
+  c.out = o;
+  int rc = nmc_call_family(x, c);
+  if (!rc) {
+    hipError_t e = hipMemcpyAsync(out, o, n * 8, hipMemcpyDeviceToHost, x->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(x->stream);
+    if (e != hipSuccess) rc = fail(-2, std::string("ppc_draws: ") + hipGetErrorString(e));
+  }
+  hipStreamSynchronize(x->stream);
+  hipFree(o);
+  return rc;
+}
+
+int nmc_ppc_partials(nmc_ctx* x, int row_begin, int n_rows, int n_valid, double* obs_state,
+                     uint32_t* obs_count, double* group_state, uint32_t* group_count, double* ty,
+                     int64_t* nonfinite) {
+  RES_PARK(x);
+  hipSetDevice(x->device);
+  if (row_begin < 0 || n_rows < 1 || row_begin > x->d.n_rows - n_rows)
+    return fail(-1, "row range out of bounds (at least one recorded row)");
+  if (n_rows >= (1 << 26)) return fail(-1, "ppc_partials: 2^26 or more rows (uint32 counts)");
+  if (n_valid < 1 || n_valid > x->C) return fail(-1, "n_valid must be in 1..n_chains");
+  if (int rc = ppc_check(x)) return rc;
+  HIPCHK(hipStreamSynchronize(x->stream));
+  if (int rc = check_timeout(x)) return rc;
+  if (int rc = ensure_waic_tiles(x)) return rc;
+  *nonfinite = 0;
+  const int CB = x->d.CB, NR = x->nresp;
+  const size_t no = (size_t)CB * NR * x->n_obs;                   // per state / count component
+  const size_t ng = (size_t)CB * x->G * NR * NMC_PPC_NSTAT;       // group tasks
+  if (ng > (size_t)0x7fffffff) return fail(-1, "ppc_partials: too many (group, field) tasks");
+  const int NS = nmc_ppc_slices(n_rows, (int64_t)CB * x->G * NR);
+  const size_t nty = (size_t)x->G * NR * NMC_PPC_NSTAT;
+  // doubles: obs states | slice states | merged group states | T(y); then the uint32 counts
+  const size_t nd = 3 * no + 3 * ng * NS + 3 * ng + nty;
+  const size_t nu = 2 * no + 2 * ng * NS + 2 * ng;
+  double* o = nullptr;
+  HIPCHK(hipMalloc(&o, nd * 8 + nu * 4));
+  double *dos = o, *dgs = dos + 3 * no, *dgm = dgs + 3 * ng * NS, *dty = dgm + 3 * ng;
+  uint32_t *uos = (uint32_t*)(o + nd), *ugs = uos + 2 * no, *ugm = ugs + 2 * ng * NS;
+  hipError_t e = hipMemsetAsync(x->wbad, 0, 8, x->stream);
+  NmcCall c;
+  c.i0 = row_begin;
+  c.i1 = row_begin + n_rows;
+  c.nc = n_valid;
+  int rc = e == hipSuccess ? nmc_event_record(x, 13) : 0;
+  if (!rc && e == hipSuccess && no > 0) {
+    c.op = NMC_OP_PPC_OBS;
+    c.out = dos;
+    c.cnt = uos;
+    rc = nmc_call_family(x, c);
+  }
+  if (!rc && e == hipSuccess) rc = nmc_event_record(x, 14);
+  if (!rc && e == hipSuccess) {
+    c.op = NMC_OP_PPC_GROUP;
+    c.out = dgs;
+    c.cnt = ugs;
+    c.aux = dty;
+    c.nb = NS;
+    rc = nmc_call_family(x, c);
+  }
+  if (!rc && e == hipSuccess) {
+    hipLaunchKernelGGL(nmc_k_ppc_group_fin, dim3((unsigned)((ng + 255) / 256)), dim3(256), 0,
+                       x->stream, (const double*)dgs, (const uint32_t*)ugs, NS, (int)ng, dgm, ugm);
+    e = hipGetLastError();
+  }
+  if (!rc && e == hipSuccess) rc = nmc_event_record(x, 15);
+  if (!rc) {
+    unsigned long long bad = 0;
+    hipStream_t st = x->stream;
+    if (e == hipSuccess && no)
+      e = hipMemcpyAsync(obs_state, dos, 3 * no * 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && no)
+      e = hipMemcpyAsync(obs_count, uos, 2 * no * 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(group_state, dgm, 3 * ng * 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(group_count, ugm, 2 * ng * 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(ty, dty, nty * 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(&bad, x->wbad, 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) rc = fail(-2, std::string("ppc_partials: ") + hipGetErrorString(e));
+    *nonfinite = (int64_t)bad;
+  }
+  hipStreamSynchronize(x->stream);
   hipFree(o);
   return rc;
 }

@@ -25,6 +25,7 @@ enum {
   NMC_PURPOSE_ACCEPT = 1,
   NMC_PURPOSE_HYPER_NORMAL = 2,
   NMC_PURPOSE_GAMMA_BOOST = 3,
+  NMC_PURPOSE_PREDICT = 4,   // posterior predictive draws (ppc.h): counter (row, obs, field, 4)
   NMC_PURPOSE_GAMMA_BASE = 16,
   NMC_GAMMA_MAX_ATTEMPTS = 64
 };

@@ -13,6 +13,8 @@
 #include <hip/hip_runtime.h>
 #include <hip/hiprtc.h>
 
+#include <string.h>
+
 #include <map>
 #include <mutex>
 #include <string>
@@ -25,9 +27,10 @@ namespace {
 // kernel table entries, in name-expression order
 // (nmc_k_run: mode m (0..4) with rows in LDS at UK_RUN0 + m, rows staged at UK_RUN0 + 5 + m;
 // the half layout at UK_HALF; WAIC's reduction, waic.h, at UK_WAIC; the LL in store layout of
-// PSIS-LOO, ll_kernels.h, at UK_LOO_LL)
+// PSIS-LOO, ll_kernels.h, at UK_LOO_LL; the posterior predictive kernels, ppc.h, at UK_PPC_*)
 enum { UK_RUN0 = 0, UK_NRUN = 5, UK_GROUP_LL = 10, UK_OBS_LL_ROWS = 11, UK_OBS_LL = 12,
-       UK_GROUP_LL_RL = 13, UK_GROUP_FIN = 14, UK_HALF = 15, UK_WAIC = 16, UK_LOO_LL = 17, UK_N = 18 };
+       UK_GROUP_LL_RL = 13, UK_GROUP_FIN = 14, UK_HALF = 15, UK_WAIC = 16, UK_LOO_LL = 17,
+       UK_PPC_DRAWS = 18, UK_PPC_OBS = 19, UK_PPC_GROUP = 20, UK_N = 21 };
 const char* const kNames[UK_N] = {
     "nmc_k_run<FamUser, 0, true>", "nmc_k_run<FamUser, 1, true>", "nmc_k_run<FamUser, 2, true>",
     "nmc_k_run<FamUser, 3, true>", "nmc_k_run<FamUser, 4, true>",
@@ -36,7 +39,8 @@ const char* const kNames[UK_N] = {
     "nmc_k_run<FamUser, 4, false>",
     "nmc_k_group_part<FamUser, false>", "nmc_k_obs_ll_rows<FamUser>",
     "nmc_k_obs_ll<FamUser>", "nmc_k_group_part<FamUser, true>", "nmc_k_group_fin<FamUser>",
-    "nmc_k_run<FamUser, 6, true>", "nmc_k_waic<FamUser>", "nmc_k_loo_ll<FamUser>"};
+    "nmc_k_run<FamUser, 6, true>", "nmc_k_waic<FamUser>", "nmc_k_loo_ll<FamUser>",
+    "nmc_k_ppc_draws<FamUser>", "nmc_k_ppc_obs<FamUser>", "nmc_k_ppc_group<FamUser>"};
 int run_index(const nmc_ctx* x, int mode) {
   if (mode == NMC_MODE_HALF) return UK_HALF;
   return UK_RUN0 + mode + (x->d.rows_lds ? 0 : UK_NRUN);
@@ -49,6 +53,7 @@ struct UserKernels {   // one device's modules, loaded on first use
 
 struct UserFamily {
   int nf = 0, np = 0;
+  int nresp = 0;                               // 1: the source defines nmc_user_predict
   std::string src;                             // the full translation unit
   std::string inc;                             // -I<csrc>
   std::vector<char> code[UK_N];                // compiled on first use, per kernel
@@ -140,6 +145,8 @@ extern "C" int nmc_user_family_compile(const char* source, int n_fields, int n_p
   UserFamily* u = new UserFamily();
   u->nf = n_fields;
   u->np = n_params;
+  // predictive (fam_user.h): the source defines the draw and names the response's field
+  u->nresp = strstr(source, "nmc_user_predict") && strstr(source, "NMC_USER_RESP") ? 1 : 0;
   // the library's own build-time kernel constants, so the JIT kernels index LDS and tiles
   // exactly as the host carve (nmc_lds / nmc_tiles) computed them
   const std::string defs = "#define NMC_NSLOT_N " + std::to_string((int)NMC_NSLOT) +
@@ -181,6 +188,7 @@ int nmc_user_attach(nmc_ctx* x, int family) {
   if (u->nf != x->nf || u->np != x->P)
     return nmc_fail(-1, "user family compiled for other n_fields / n_params");
   x->user = u;
+  x->nresp = u->nresp;
   return 0;
 }
 
@@ -280,6 +288,51 @@ int nmc_call_user(nmc_ctx* x, NmcCall& c) {
       if (int rc = user_fn(x, UK_WAIC, &f)) return rc;
       return launch(x, f, dim3((unsigned)((x->n_wtiles + 3) / 4), (unsigned)d0.CB), dim3(256),
                     0, args);
+    }
+    case NMC_OP_PPC_DRAWS: {
+      const int n = c.i1 - c.i0;
+      if (n <= 0 || x->n_obs == 0) return 0;
+      Dev dd = d0;
+      const int* gidx = (const int*)x->gidx;
+      int64_t n_obs = x->n_obs;
+      int pc = x->pooling == NMC_POOL_PARTIAL ? 2 : 0, row0 = c.i0, nrows = n;
+      double* out = c.out;
+      void* args[] = {&dd, &fam, (void*)&gidx, &n_obs, &pc, &row0, &nrows, &out};
+      if (int rc = user_fn(x, UK_PPC_DRAWS, &f)) return rc;
+      return launch(x, f,
+                    dim3((unsigned)((x->n_obs + 255) / 256), (unsigned)x->C, (unsigned)n),
+                    dim3(256), 0, args);
+    }
+    case NMC_OP_PPC_OBS: {
+      if (x->n_wtiles == 0) return 0;
+      Dev dd = d0;
+      const double* obs = d0.obs;
+      const nmc_waic_tile* tiles = x->wtiles;
+      int ntiles = x->n_wtiles;
+      int64_t n_obs = x->n_obs;
+      int pc = x->pooling == NMC_POOL_PARTIAL ? 2 : 0, row0 = c.i0, nrows = c.i1 - c.i0;
+      int n_valid = c.nc;
+      double* out = c.out;
+      uint32_t* cnt = c.cnt;
+      unsigned long long* bad = x->wbad;
+      void* args[] = {&dd, &fam, (void*)&obs, (void*)&tiles, &ntiles, &n_obs, &pc, &row0,
+                      &nrows, &n_valid, &out, &cnt, &bad};
+      if (int rc = user_fn(x, UK_PPC_OBS, &f)) return rc;
+      return launch(x, f, dim3((unsigned)((x->n_wtiles + 3) / 4), (unsigned)d0.CB), dim3(256),
+                    0, args);
+    }
+    case NMC_OP_PPC_GROUP: {   // (FamUser::NRESP = 1)
+      Dev dd = d0;
+      const double* obs = d0.obs;
+      int pc = x->pooling == NMC_POOL_PARTIAL ? 2 : 0, row0 = c.i0, nrows = c.i1 - c.i0;
+      int n_valid = c.nc;
+      double* out = c.out;
+      uint32_t* cnt = c.cnt;
+      double* ty = c.aux;
+      void* args[] = {&dd, &fam, (void*)&obs, &pc, &row0, &nrows, &n_valid, &out, &cnt, &ty};
+      if (int rc = user_fn(x, UK_PPC_GROUP, &f)) return rc;
+      return launch(x, f, dim3((unsigned)x->G, (unsigned)d0.CB, (unsigned)c.nb), dim3(256), 0,
+                    args);
     }
     case NMC_OP_LOO_LL: {
       int nrows = c.i1 - c.i0, nb = c.nb;

@@ -66,6 +66,11 @@ SIGNATURES = {
     "nmc_write_ll_csvs": (ctypes.c_int, [_vp, ctypes.c_char_p, _c_int32_p, ctypes.c_int]),
     "nmc_waic_partials": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                          _c_double_p, _c_int64_p]),
+    "nmc_ppc_nresp": (ctypes.c_int, [_vp, _c_int_p]),
+    "nmc_ppc_draws": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _c_double_p]),
+    "nmc_ppc_partials": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                        _c_double_p, _c_uint32_p, _c_double_p, _c_uint32_p,
+                                        _c_double_p, _c_int64_p]),
     "nmc_conv_partials": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                          _c_double_p, _c_double_p, _c_double_p]),
     "nmc_summary": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,

@@ -253,6 +253,69 @@ class Engine:
         parts = self.waic_partials(row_begin, n_rows, n_valid)
         return _waic.finish(_waic.merge(list(parts)), self.off)
 
+    # -- posterior predictive checks (nestmc.ppc; csrc/ppc.h) -------------------------------
+    def n_resp(self):
+        """The response fields the family can draw replicates of (0: it cannot draw)."""
+        n = ctypes.c_int()
+        check(self.lib.nmc_ppc_nresp(self.h, ctypes.byref(n)))
+        return n.value
+
+    def observed(self):
+        """y [n_obs, NRESP]: the family's table at its response fields."""
+        return numpy.ascontiguousarray(self._keep[0][:, list(self.family.response_fields())])
+
+    def predictive_draws(self, row_begin=0, n_rows=None):
+        """The posterior predictive replicates at recorded rows of the sample store,
+        [C, rows, n_obs, NRESP] (nmc_ppc_draws): for small windows, tests and statistics of
+        one's own -- Engine.ppc never forms them."""
+        if n_rows is None:
+            n_rows = self.n_rows - row_begin
+        out = numpy.empty((self.C, max(int(n_rows), 0), int(self.off[-1]), max(self.n_resp(), 1)))
+        check(self.lib.nmc_ppc_draws(self.h, int(row_begin), int(n_rows), dptr(out)))
+        return out
+
+    def ppc_partials_raw(self, row_begin=0, n_rows=None, n_valid=None):
+        """nmc_ppc_partials as it answers: (the chain blocks' partials, a list of nestmc.ppc
+        dicts in chain-block order, each with nonfinite = 0; the call's non-finite count)."""
+        if n_rows is None:
+            n_rows = self.n_rows - row_begin
+        if n_valid is None:
+            n_valid = self.C
+        CB, n, NR = (self.C + 63) // 64, int(self.off[-1]), max(self.n_resp(), 1)
+        ost = numpy.empty((CB, 3, NR, n))
+        oct_ = numpy.empty((CB, 2, NR, n), dtype=numpy.uint32)
+        gst = numpy.empty((CB, self.G, NR, 4, 3))
+        gct = numpy.empty((CB, self.G, NR, 4, 2), dtype=numpy.uint32)
+        ty = numpy.empty((self.G, NR, 4))
+        bad = ctypes.c_int64()
+        u32 = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))   # noqa: E731
+        check(self.lib.nmc_ppc_partials(self.h, int(row_begin), int(n_rows), int(n_valid),
+                                        dptr(ost), u32(oct_), dptr(gst), u32(gct), dptr(ty),
+                                        ctypes.byref(bad)))
+        parts = [dict(obs_state=ost[b], obs_count=oct_[b].astype(numpy.int64),
+                      group_state=gst[b], group_count=gct[b].astype(numpy.int64), ty=ty,
+                      nonfinite=0) for b in range(CB)]
+        return parts, bad.value
+
+    def ppc_partials(self, row_begin=0, n_rows=None, n_valid=None):
+        """The posterior predictive partials of every chain block over recorded rows
+        [row_begin, row_begin + n_rows) and local chains [0, n_valid), reduced on the device
+        from the sample store (nmc_ppc_partials; nestmc.ppc): a list of dicts in chain-block
+        order.  Chains from n_valid on (padding) enter as the identity.  A draw that is not
+        finite is an error."""
+        parts, bad = self.ppc_partials_raw(row_begin, n_rows, n_valid)
+        self.ppc_nonfinite = bad
+        if bad:
+            raise _lib.NestmcError("posterior predictive checks: %d draws were not finite" % bad)
+        return parts
+
+    def ppc(self, row_begin=0, n_rows=None, n_valid=None):
+        """The PpcResult (nestmc.ppc) of this engine's chains: its chain blocks' partials
+        merged in chain-block order."""
+        from . import ppc as _ppc
+        parts = self.ppc_partials(row_begin, n_rows, n_valid)
+        return _ppc.finish(_ppc.merge(parts), self.off, self.observed())
+
     def loo_raw(self, row_begin=0, n_rows=None, n_valid=None, obs_batch=0):
         """PSIS-LOO's per-observation results over recorded rows [row_begin, row_begin +
         n_rows) and local chains [0, n_valid), computed on the device from the sample store

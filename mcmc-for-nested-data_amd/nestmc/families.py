@@ -43,6 +43,13 @@ class Family:
         from . import _lib
         return _lib.FAMILY[self.family]
 
+    response_integer = False   # the response takes integer values (csrc/families.h RESP_INT)
+
+    def response_fields(self):
+        """The fields of obs() the family can draw posterior predictive replicates of
+        (nestmc.ppc; csrc/families.h NRESP and resp_field); empty: it cannot draw."""
+        return []
+
     def __call__(self, parameter):
         raise NotImplementedError
 
@@ -94,6 +101,9 @@ class LinearRegression(Family):
             return [float(k), float(self.intercept), 0.0, 0.0]
         return [float(k), float(self.intercept), self.sigma, float(numpy.log(self.sigma))]
 
+    def response_fields(self):
+        return [self.n_fields - 1]
+
     def __call__(self, parameter):
         K = self.X.shape[1]
         betaHat = numpy.vstack([parameter[j] for j in range(K)]).T
@@ -134,6 +144,9 @@ class GaussianMean(Family):
     def consts(self):
         return list(self.sd) + list(numpy.log(self.sd))
 
+    def response_fields(self):
+        return list(range(self.n_fields))
+
     def __call__(self, parameter):
         out = 0
         for j in range(self.n_params):
@@ -150,6 +163,7 @@ class Logistic(Family):
     """
 
     family = "logistic"
+    response_integer = True
 
     def __init__(self, X, y):
         self.X, stored, self.intercept = _split_intercept(X)
@@ -165,6 +179,9 @@ class Logistic(Family):
 
     def consts(self):
         return [float(self.n_fields - 1), float(self.intercept), 0.0, 0.0]
+
+    def response_fields(self):
+        return [self.n_fields - 1]
 
     def __call__(self, parameter):
         theta = numpy.vstack(parameter).T
@@ -197,6 +214,19 @@ class DeviceLikelihood(Family):
     parameters up to 128 groups (9 to 12 by the group count modulo 8) and fewer over more
     groups; the engine refuses a model beyond that when it is created.
 
+    Posterior predictive checks (nestmc.ppc) need a draw from the likelihood: a source that
+    also defines::
+
+        __device__ double nmc_user_predict(const double* theta, const double* row,
+                                           const double* k, double ua, double ub, double z)
+        { ... }   // one replicate of row[response_field]
+
+    (ua, ub: two uniforms in [0, 1); z: their Box-Muller normal) is predictive;
+    ``response_field`` names the field it replicates (default: the last);
+    ``response_integer=True`` says the response takes integer values (counts, 0 / 1): the
+    groups' mean and variance then come from exact sums, so a replicate that ties with the
+    data compares equal whatever the order of its values.
+
     ``host_function(parameter[P][n]) -> ll[n]`` (optional) is the same model in the
     reference's calling convention; the host needs it only for ``startWithMLE`` (the
     Nelder-Mead objective, :1102-1141) -- every other evaluation runs on the device.
@@ -204,7 +234,8 @@ class DeviceLikelihood(Family):
 
     family = "user"
 
-    def __init__(self, obs, source, n_params, consts=(), host_function=None):
+    def __init__(self, obs, source, n_params, consts=(), host_function=None,
+                 response_field=None, response_integer=False):
         obs = numpy.asarray(obs, dtype=numpy.float64)
         if obs.ndim == 1:
             obs = obs[:, None]
@@ -217,6 +248,21 @@ class DeviceLikelihood(Family):
             raise ValueError("1 <= n_params <= 16")
         if "nmc_user_loglik" not in source:
             raise ValueError("source must define __device__ double nmc_user_loglik(...)")
+        # predictive (nestmc.ppc): the source defines nmc_user_predict, the replicate of
+        # row[response_field] (default: the last field); the define goes in front of the source
+        self.response_field = None
+        self.response_integer = bool(response_integer) and "nmc_user_predict" in source
+        if "nmc_user_predict" in source:
+            rf = self.n_fields - 1 if response_field is None else int(response_field)
+            if not 0 <= rf < self.n_fields:
+                raise ValueError("response_field must be in 0..n_fields-1")
+            self.response_field = rf
+            source = "#define NMC_USER_RESP %d\n" % rf + source
+            if response_integer:
+                source = "#define NMC_USER_RESP_INT 1\n" + source
+        elif response_field is not None:
+            raise ValueError("response_field needs a source that defines __device__ double "
+                             "nmc_user_predict(theta, row, k, ua, ub, z)")
         self.source = source
         self._consts = [float(v) for v in consts]
         self.host_function = host_function
@@ -236,6 +282,9 @@ class DeviceLikelihood(Family):
                                                    ctypes.byref(fid)))
             _USER_IDS[key] = fid.value
         return _USER_IDS[key]
+
+    def response_fields(self):
+        return [] if self.response_field is None else [self.response_field]
 
     def obs(self):
         return self._obs

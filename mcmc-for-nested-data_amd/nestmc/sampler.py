@@ -29,6 +29,7 @@ from . import groupcmp as _groupcmp
 from . import summary as _summary
 from . import loo as _loo
 from . import rankdiag as _rankdiag
+from . import ppc as _ppc
 from . import waic as _waic
 from .engine import Engine
 from .families import is_family
@@ -70,7 +71,8 @@ def sample_posterior(nChains, nIter, nSamples, parameterName, nGroups, nResponse
                      write_files=True, replay=None, process_per_device=False, _rank=None,
                      computeWaic=False, computeDiagnostics=False, computeSummary=False,
                      computeLoo=False, computeRankDiagnostics=False,
-                     computeGroupComparison=False, computeCorrelation=False):
+                     computeGroupComparison=False, computeCorrelation=False,
+                     computePredictiveChecks=False):
     """Drop-in for posteriorSampling.samplePosterior (same positional/keyword API).
 
     Extra keyword-only options (all optional):
@@ -153,6 +155,17 @@ def sample_posterior(nChains, nIter, nSamples, parameterName, nGroups, nResponse
                  process_per_device are merged by Chan's update: within rounding of the one
                  engine's numbers, not bit-identical.  Fewer than two samples raise ValueError
                  before sampling starts
+      computePredictiveChecks  after the loop, draw on the GPU a replicated data set from every
+                 recorded sample and compare it with the observed data (nestmc.ppc; the
+                 replicates are reduced where they are drawn and never leave the device): per
+                 observation the predictive mean, sd, standardised residual and PIT, per group
+                 the posterior predictive p-values of its mean, variance, minimum and maximum:
+                 outputDirectory/ppc_groups.csv and ppc_pointwise.csv, "predictive_checks" (a
+                 nestmc.ppc.PpcResult) in the returned dict and one warning line naming the
+                 groups and statistics with p < 0.025 or p > 0.975.  Any number of engines and
+                 ranks (merged in engine and rank order: counts exactly, moments by Chan's
+                 update).  A family that cannot draw (a DeviceLikelihood without
+                 nmc_user_predict) raises ValueError before sampling starts
     nProcesses sizes the host threads used for chain initialisation and CSV writing.
     """
     start_time = datetime.datetime.now()
@@ -184,6 +197,10 @@ def sample_posterior(nChains, nIter, nSamples, parameterName, nGroups, nResponse
     if computeGroupComparison and (pooling == "complete" or nGroups < 2):
         raise ValueError("computeGroupComparison compares a parameter's groups with each other: "
                          "it needs at least two groups (pooling='complete' has one)")
+    if computePredictiveChecks and not logLikelihoodFunction.response_fields():
+        raise ValueError("computePredictiveChecks needs a family that can draw from its "
+                         "likelihood: this DeviceLikelihood's source does not define "
+                         "nmc_user_predict (INTEGRATION.md, 'Posterior predictive checks')")
     names = tuple(parameterName)
     if len(names) != logLikelihoodFunction.n_params:
         raise ValueError("parameterName has %d names, the likelihood family has %d parameters"
@@ -231,6 +248,8 @@ def sample_posterior(nChains, nIter, nSamples, parameterName, nGroups, nResponse
                              "recorded rows of all chains give %d" % n_val)
     if computeLoo and len(record_iterations(nIter, burn, thin)) * nChains < 2:
         raise ValueError("computeLoo needs at least two samples")
+    if computePredictiveChecks and len(record_iterations(nIter, burn, thin)) * nChains < 2:
+        raise ValueError("computePredictiveChecks needs at least two samples")
     if computeCorrelation:
         n_val = len(record_iterations(nIter, burn, thin)) * \
             (nChains if chains is None else len(chains))
@@ -274,7 +293,8 @@ def sample_posterior(nChains, nIter, nSamples, parameterName, nGroups, nResponse
                   computeWaic=computeWaic, computeDiagnostics=computeDiagnostics,
                   computeSummary=computeSummary,
                   computeGroupComparison=computeGroupComparison,
-                  computeCorrelation=computeCorrelation)
+                  computeCorrelation=computeCorrelation,
+                  computePredictiveChecks=computePredictiveChecks)
         res = ranks.run_per_device(kw, devices)
         _finish_log(logger, [], start_time, displayProgress)
         return res
@@ -357,7 +377,8 @@ def sample_posterior(nChains, nIter, nSamples, parameterName, nGroups, nResponse
                             compute_summary=bool(computeSummary), compute_loo=bool(computeLoo),
                             compute_rank=bool(computeRankDiagnostics),
                             compute_group=bool(computeGroupComparison),
-                            compute_corr=bool(computeCorrelation))
+                            compute_corr=bool(computeCorrelation),
+                            compute_ppc=bool(computePredictiveChecks))
     finally:
         for eng, _, _ in engines:
             eng.close()
@@ -422,6 +443,33 @@ def _waic_of(engines, rank_info, n_real):
         part = _waic.merge_ranks([numpy.frombuffer(b, dtype=numpy.float64).reshape(5, -1)
                                   for b in got])
     return _waic.finish(part, off)
+
+
+def _ppc_of(engines, rank_info, n_real):
+    """computePredictiveChecks: every engine's chain-block partials over all recorded rows (its
+    padding chains, ids >= n_real, as the identity), merged in engine order; the ranks of
+    process_per_device send theirs over the host group and rank 0 merges them in rank order
+    and finishes (the other ranks: None).  A draw that is not finite is an error."""
+    eng0 = engines[0][0]
+    parts = []
+    for eng, _, ids in engines:
+        n_valid = sum(1 for c in ids if c < n_real)
+        if n_valid > 0:
+            blocks, bad = eng.ppc_partials_raw(n_valid=n_valid)
+            blocks[0]["nonfinite"] = bad
+            parts.extend(blocks)
+        else:
+            parts.append(_ppc.identity(int(eng.off[-1]), eng.G, eng.n_resp()))
+    part = _ppc.merge(parts)
+    if rank_info is not None:
+        got = rank_info["hg"].gather(_ppc.pack(part))
+        if rank_info["rank"] != 0:
+            return None
+        part = _ppc.merge_ranks([_ppc.unpack(b) for b in got])
+    if part["nonfinite"]:
+        raise _lib.NestmcError("posterior predictive checks: %d draws were not finite"
+                               % part["nonfinite"])
+    return _ppc.finish(part, eng0.off, eng0.observed())
 
 
 def _conv_of(engines, rank_info, n_real, header):
@@ -548,7 +596,7 @@ def _sample_loop(engines, nIter, burn, thin, names, G, partial, saveLogLikelihoo
                  sample_dir, threads, displayProgress, return_samples, logger, chain_logs,
                  start_time, rank_info=None, compute_waic=False, waic_dir=None,
                  n_real=None, compute_conv=False, compute_summary=False, compute_loo=False,
-                 compute_rank=False, compute_group=False, compute_corr=False):
+                 compute_rank=False, compute_group=False, compute_corr=False, compute_ppc=False):
     """The device loop, the per-observation LL rows and the sample files of
     sample_posterior (the caller closes the engines whatever happens here).  rank_info: a
     rank of process_per_device -- this rank writes its chains' logLikelihood files, rank 0
@@ -624,6 +672,18 @@ def _sample_loop(engines, nIter, burn, thin, names, G, partial, saveLogLikelihoo
         corr_result = _correlation_of(engines, rank_info, n_real, header)
         if corr_result is not None and write_files:
             _correlation.write_csvs(corr_result, waic_dir, len(names), G, partial)
+    ppc_result = None
+    if compute_ppc:
+        ppc_result = _ppc_of(engines, rank_info, n_real)
+        if ppc_result is not None:
+            if write_files:
+                _ppc.write_csvs(ppc_result, waic_dir)
+            warn = ppc_result.warning()
+            if warn:
+                if logger:
+                    logger.warning(warn)
+                if displayProgress:
+                    output.print_progress(warn)
     summary_result = None
     if compute_summary:
         summary_result = _summary_of(engines, rank_info, n_real, header)
@@ -672,6 +732,8 @@ def _sample_loop(engines, nIter, burn, thin, names, G, partial, saveLogLikelihoo
             res["group_comparison"] = group_result
         if corr_result is not None:
             res["correlation"] = corr_result
+        if ppc_result is not None:
+            res["predictive_checks"] = ppc_result
         if summary_result is not None:
             res["summary"] = summary_result
             if conv_result is not None:

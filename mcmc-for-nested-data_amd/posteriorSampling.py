@@ -26,7 +26,8 @@ def samplePosterior(nChains, nIter, nSamples,
                     nProcesses=1, displayProgress=True, loggingLevel="info",
                     computeWaic=False, computeDiagnostics=False, computeSummary=False,
                     computeLoo=False, computeRankDiagnostics=False,
-                    computeGroupComparison=False, computeCorrelation=False, **gpu_options):
+                    computeGroupComparison=False, computeCorrelation=False,
+                    computePredictiveChecks=False, **gpu_options):
     """Sample the posterior of a nested model; samples go to outputDirectory/sample/.
 
     Arguments mirror the reference (posteriorSampling.py:28-145).  Keyword-only
@@ -47,7 +48,10 @@ def samplePosterior(nChains, nIter, nSamples,
     nestmc.groupcmp) -- at least two groups, any number of engines.  computeCorrelation=True
     also computes the posterior covariance and correlation matrix of all columns on the GPU
     (correlation.csv, correlation_pairs.csv; nestmc.correlation) -- at least two samples, any
-    number of engines.  Returns None like the reference unless return_samples=True.
+    number of engines.  computePredictiveChecks=True also draws a replicated data set from
+    every recorded sample on the GPU and compares it with the observed data, per observation
+    and per group (ppc_groups.csv, ppc_pointwise.csv; nestmc.ppc) -- a built-in family or a
+    DeviceLikelihood with nmc_user_predict, any number of engines.  Returns None like the reference unless return_samples=True.
     """
     return sample_posterior(nChains, nIter, nSamples, parameterName, nGroups,
                             nResponsesPerGroup, pooling, logLikelihoodFunction,
@@ -60,4 +64,5 @@ def samplePosterior(nChains, nIter, nSamples,
                             computeSummary=computeSummary, computeLoo=computeLoo,
                             computeRankDiagnostics=computeRankDiagnostics,
                             computeGroupComparison=computeGroupComparison,
-                            computeCorrelation=computeCorrelation, **gpu_options)
+                            computeCorrelation=computeCorrelation,
+                            computePredictiveChecks=computePredictiveChecks, **gpu_options)
