@@ -247,6 +247,41 @@ int nmc_ppc_draws(nmc_ctx* ctx, int row_begin, int n_rows, double* out);
 int nmc_ppc_partials(nmc_ctx* ctx, int row_begin, int n_rows, int n_valid, double* obs_state,
                      uint32_t* obs_count, double* group_state, uint32_t* group_count, double* ty,
                      int64_t* nonfinite);
+/* Held-out rows and new groups (csrc/predict.h; no counterpart in the reference): the family's
+ * density and draw on a table other than the training table, from the sample store.
+ * nmc_predict_set: new_obs[n_new][n_fields] in the family's row layout (n_fields = the
+ * context's width) and new_group[n_new]: a code g >= 0 is training group g, -(k + 1) is new
+ * group k, 0 <= k < n_new_groups (partial pooling only), whose values at recorded row r and
+ * chain c are mu_q + sqrt(sigma2_q) z from that sample's hyper columns, z the normal of the
+ * Philox block with counter (r, k, q, purpose 5) and key (chain_base + c, seed); NaN where
+ * sigma2_q is not > 0 or not finite.  The call copies the table, cuts it into tiles (at every
+ * change of the code and every 8 rows) and replaces the table in place; new_obs = NULL with
+ * n_new = 0 clears it; nmc_destroy frees it.  -1 and nothing changed: another width, a code
+ * >= G or < -n_new_groups, a new group without partial pooling, n_new >= 2^32.
+ * A row has a held-out response when all its response fields (nmc_ppc_nresp's) are finite; a
+ * draw y_rep of response field j of new row i is the family's predict() on the block with
+ * counter (r, i, j, purpose 6): it depends on (seed, global chain, r, i, j) and theta alone.
+ * nmc_predict_draws: yrep[C][n_rows][n_new][nresp], ll[C][n_rows][n_new] (the log density of
+ * row i at the sample's values) and theta_new[C][n_rows][n_new_groups][P]; each may be NULL
+ * (at most 65535 rows per call).  yrep needs a family that can draw.
+ * nmc_predict_partials: over recorded rows [row_begin, row_begin + n_rows) and local chains
+ * [0, n_valid), per chain block (CB = ceil(C / 64)):
+ *   dens[CB][2][n_new]            m = max ll, s = sum exp(ll - m)  (nmc_waic_partials' words)
+ *   state[CB][3][nresp][n_new]    n, Welford's mean and M2 of y_rep over the samples
+ *   count[CB][2][nresp][n_new]    lt = #{y_rep < y}, eq = #{y_rep == y}  (0 without a response)
+ * merged in the fixed order csrc/predict.h documents; nestmc/predict.py merges the blocks and
+ * finishes.  dens may be NULL, and state with count (a family that cannot draw has the
+ * density only; asking it for state is refused as nmc_ppc_draws refuses).  Chains >= n_valid
+ * enter as the identity.  n_rows < 2^26 (uint32 counts); other argument errors as
+ * nmc_waic_partials.  *nonfinite_draws: draws that were not finite; *nonfinite_ll: ll terms
+ * that were not finite at rows WITH a response.  Event slots 16 and 17 bracket the kernel. */
+int nmc_predict_set(nmc_ctx* ctx, const double* new_obs, int64_t n_new, int n_fields,
+                    const int32_t* new_group, int n_new_groups);
+int nmc_predict_draws(nmc_ctx* ctx, int row_begin, int n_rows, double* yrep, double* ll,
+                      double* theta_new);
+int nmc_predict_partials(nmc_ctx* ctx, int row_begin, int n_rows, int n_valid, double* dens,
+                         double* state, uint32_t* count, int64_t* nonfinite_draws,
+                         int64_t* nonfinite_ll);
 /* The convergence diagnostic's partial sums (Diagnostic, sampleDiagnosis.py:136-255: the split
  * of every chain into two halves :136-155, the means and variances of :158-187, the variogram
  * of :189-194) over recorded rows [row_begin, row_begin + n_rows) and local chains
@@ -399,7 +434,7 @@ int nmc_comoments_of(int device, const double* x, int rows, int cols, int C, int
                      double* mean, double* minmax, double* M, int64_t* nonfinite);
 
 /* Timing on the context's stream (hipEvents). */
-int nmc_event_record(nmc_ctx* ctx, int slot);                 /* slot 0..15 */
+int nmc_event_record(nmc_ctx* ctx, int slot);                 /* slot 0..17 */
 int nmc_event_elapsed(nmc_ctx* ctx, int slot_a, int slot_b, float* ms);
 /* Bracket every step launch with events (adds a little overhead): per-kernel
  * average duration for the roofline; step_iters = iterations those launches ran. */

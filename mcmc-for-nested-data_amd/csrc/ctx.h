@@ -48,6 +48,8 @@ int nmc_fail(int code, const std::string& msg);
       return nmc_fail(-2, std::string(#x) + ": " + hipGetErrorString(e_));            \
   } while (0)
 
+enum { NMC_NEV = 18 };   // event slots of nmc_event_record (include/nestmc.h)
+
 struct nmc_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -76,7 +78,7 @@ struct nmc_ctx {
   int n_iter = 0;
   bool scheduled = false;
   bool trace = false;
-  hipEvent_t ev[16] = {};
+  hipEvent_t ev[NMC_NEV] = {};
   bool ktiming = false;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> kev;   // step launches
   std::vector<std::pair<hipEvent_t, hipEvent_t>> hev;   // hyper-only launches
@@ -97,6 +99,14 @@ struct nmc_ctx {
   int n_wtiles = 0;
   unsigned long long* wbad = nullptr;     // non-finite terms nmc_k_waic met (zeroed per call)
   int nresp = 0;                          // response fields the family can draw (ppc.h; 0: none)
+  // the new table of nmc_predict_set (predict.h); its buffers are replaced by every call of it
+  double* pobs = nullptr;                 // [n_pnew][nf] new rows
+  int* pgrp = nullptr;                    // [n_pnew] group codes (g, or -(k + 1): new group k)
+  nmc_waic_tile* ptiles = nullptr;        // [n_ptiles] runs of <= NMC_WAIC_T rows with one code
+  int n_ptiles = 0;
+  int64_t n_pnew = 0;
+  int pK = 0;                             // new groups
+  unsigned long long* pbad = nullptr;     // [2] non-finite draws, ll terms (zeroed per call)
   int split_batch = 0;                    // row split: chain blocks per (resident) launch
   int sweep_batch = 0;                    // nmc_k_sweep with Dev.gsep: chain blocks per launch
   unsigned gepoch = 0;                    // Dev.gsep launches so far (Dev.gep)
@@ -128,8 +138,8 @@ struct nmc_ctx {
     int fill_minb = 1;                    // nmc_k_fill instance that fits beside the launch
     std::chrono::steady_clock::time_point t_post;   // (NMC_TRACE_CALLS: the latest post)
     std::vector<std::pair<unsigned, double>> spans;   // (seq, GPU ms) of continued calls
-    bool ev_res[16] = {};                 // event slot recorded as a resident marker
-    unsigned ev_seq[16] = {};
+    bool ev_res[NMC_NEV] = {};            // event slot recorded as a resident marker
+    unsigned ev_seq[NMC_NEV] = {};
   } res;
 };
 
@@ -279,8 +289,14 @@ enum {
   NMC_OP_PPC_DRAWS = 9,    // sample rows [i0, i1) -> out = [C][i1 - i0][n_obs][NRESP] (ppc.h)
   NMC_OP_PPC_OBS = 10,     // sample rows [i0, i1), chains < nc valid -> out = [CB][3][NRESP][n_obs],
                            // cnt = [CB][2][NRESP][n_obs]
-  NMC_OP_PPC_GROUP = 11    // the same rows and chains in nb slices -> out = [nb][CB][G][NRESP][4][3],
+  NMC_OP_PPC_GROUP = 11,   // the same rows and chains in nb slices -> out = [nb][CB][G][NRESP][4][3],
                            // cnt = [nb][CB][G][NRESP][4][2], aux = T(y) [G][NRESP][4]
+  NMC_OP_PREDICT = 12,     // sample rows [i0, i1), chains < nc valid, the new table ->
+                           // aux = [CB][2][n_new] (m, s), out = [CB][3][NRESP][n_new],
+                           // cnt = [CB][2][NRESP][n_new]; aux or out null: that pass is left out
+  NMC_OP_PREDICT_DRAWS = 13   // sample rows [i0, i1), the new table -> out = yrep
+                           // [C][i1 - i0][n_new][NRESP], aux = ll [C][i1 - i0][n_new], aux2 =
+                           // theta_new [C][i1 - i0][K][P]; each may be null
 };
 struct NmcCall {
   int op = 0;
@@ -293,6 +309,7 @@ struct NmcCall {
   const double* in = nullptr;
   double* out = nullptr;
   double* aux = nullptr;   // op-specific device scratch
+  double* aux2 = nullptr;  // NMC_OP_PREDICT_DRAWS: theta_new
   uint32_t* cnt = nullptr; // NMC_OP_PPC_*: the integer counts
   int result = 0;
   int result2 = 0;         // NMC_OP_RES_OK: the resident instance's VGPRs per lane

@@ -151,6 +151,27 @@ static int nmc_fam_call(nmc_ctx* x, const Fam& fam, NmcCall& c) {
       HIPCHK(hipGetLastError());
       return 0;
     }
+    case NMC_OP_PREDICT: {
+      if (x->n_ptiles == 0) return 0;
+      const dim3 grid((unsigned)((x->n_ptiles + 3) / 4), (unsigned)x->d.CB);
+      hipLaunchKernelGGL(nmc_k_predict<Fam>, grid, dim3(256), 0, x->stream, x->d, fam,
+                         (const double*)x->pobs, (const nmc_waic_tile*)x->ptiles, x->n_ptiles,
+                         x->n_pnew, x->pooling == NMC_POOL_PARTIAL ? 2 : 0, c.i0, c.i1 - c.i0,
+                         c.nc, c.aux, c.out, c.cnt, x->pbad);
+      HIPCHK(hipGetLastError());
+      return 0;
+    }
+    case NMC_OP_PREDICT_DRAWS: {
+      const int n = c.i1 - c.i0;
+      const int64_t slots = std::max<int64_t>(x->n_pnew, x->pK);
+      if (n <= 0 || slots == 0) return 0;
+      const dim3 grid((unsigned)((slots + 255) / 256), (unsigned)x->C, (unsigned)n);
+      hipLaunchKernelGGL(nmc_k_predict_draws<Fam>, grid, dim3(256), 0, x->stream, x->d, fam,
+                         (const double*)x->pobs, (const int*)x->pgrp, x->n_pnew, x->pK,
+                         x->pooling == NMC_POOL_PARTIAL ? 2 : 0, c.i0, n, c.out, c.aux, c.aux2);
+      HIPCHK(hipGetLastError());
+      return 0;
+    }
     case NMC_OP_LOO_LL: {
       const int n = c.i1 - c.i0;
       if (n <= 0 || c.nb <= 0) return 0;

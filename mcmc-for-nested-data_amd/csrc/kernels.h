@@ -46,3 +46,4 @@
 #include "ll_kernels.h"  // group and per-observation log-likelihood kernels
 #include "waic.h"        // WAIC: per-observation reduction over the sample store
 #include "ppc.h"         // posterior predictive draws and their reductions over the store
+#include "predict.h"     // held-out rows and new groups: draws, densities and their reduction

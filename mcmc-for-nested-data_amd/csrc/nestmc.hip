@@ -826,7 +826,7 @@ int nmc_destroy(nmc_ctx* x) {
   if (x->stream) hipStreamSynchronize(x->stream);
   if (x->gstream) hipStreamSynchronize(x->gstream);
   if (x->pstream) hipStreamSynchronize(x->pstream);
-  for (void* p : x->owned) if (p) hipFree(p);
+  for (void* p : x->owned) if (p) hipFree(p);   // (the new table of nmc_predict_set among them)
   for (auto& ev : x->ev) if (ev) hipEventDestroy(ev);
   for (auto& pr : x->kev) { hipEventDestroy(pr.first); hipEventDestroy(pr.second); }
   for (auto& pr : x->hev) { hipEventDestroy(pr.first); hipEventDestroy(pr.second); }
@@ -1334,7 +1334,7 @@ int nmc_eval_obs_ll(nmc_ctx* x, double* out) {
 // the sum of the GPU spans (s_memrealtime: workgroup 0 taking the call, or starting the
 // launch for its first call -> the last workgroup done) of the calls issued since slot a.
 int nmc_event_record(nmc_ctx* x, int slot) {
-  if (slot < 0 || slot >= 16) return fail(-1, "event slot 0..15");
+  if (slot < 0 || slot >= NMC_NEV) return fail(-1, "event slot 0..17");
   hipSetDevice(x->device);
   x->res.ev_res[slot] = x->res.active;
   x->res.ev_seq[slot] = x->res.seq;
@@ -1343,7 +1343,7 @@ int nmc_event_record(nmc_ctx* x, int slot) {
 }
 
 int nmc_event_elapsed(nmc_ctx* x, int a, int b, float* ms) {
-  if (a < 0 || a >= 16 || b < 0 || b >= 16) return fail(-1, "event slot 0..15");
+  if (a < 0 || a >= NMC_NEV || b < 0 || b >= NMC_NEV) return fail(-1, "event slot 0..17");
   hipSetDevice(x->device);
   auto& r = x->res;
   if (r.ev_res[b]) {   // (a: a marker, or an event recorded before the launch started)
@@ -1817,6 +1817,166 @@ int nmc_ppc_partials(nmc_ctx* x, int row_begin, int n_rows, int n_valid, double*
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) rc = fail(-2, std::string("ppc_partials: ") + hipGetErrorString(e));
     *nonfinite = (int64_t)bad;
+  }
+  hipStreamSynchronize(x->stream);
+  hipFree(o);
+  return rc;
+}
+
+// ---------------------------------------------------------------------------
+// Held-out rows and new groups (predict.h; include/nestmc.h)
+// ---------------------------------------------------------------------------
+static void predict_free(nmc_ctx* x) {
+  dfree(x, x->pobs);
+  dfree(x, x->pgrp);
+  dfree(x, x->ptiles);
+  x->pobs = nullptr;
+  x->pgrp = nullptr;
+  x->ptiles = nullptr;
+  x->n_ptiles = 0;
+  x->n_pnew = 0;
+  x->pK = 0;
+}
+
+// The new table to the device with its tile table: a tile ends at every change of the group
+// code and after NMC_WAIC_T rows.  Everything is checked before the table in place is touched.
+int nmc_predict_set(nmc_ctx* x, const double* new_obs, int64_t n_new, int n_fields,
+                    const int32_t* new_group, int n_new_groups) {
+  RES_PARK(x);
+  hipSetDevice(x->device);
+  if (!new_obs || n_new == 0) {
+    if (n_new != 0) return fail(-1, "predict_set: new_obs is NULL");
+    HIPCHK(hipStreamSynchronize(x->stream));
+    predict_free(x);
+    return 0;
+  }
+  if (!new_group) return fail(-1, "predict_set: new_group is NULL");
+  if (n_fields != x->nf)
+    return fail(-1, "predict_set: the new table has " + std::to_string(n_fields) +
+                        " fields, the family's rows have " + std::to_string(x->nf));
+  if (n_new < 0 || n_new >= ((int64_t)1 << 32))
+    return fail(-1, "predict_set: 2^32 or more new observations");
+  if (n_new_groups < 0) return fail(-1, "predict_set: n_new_groups is negative");
+  if (n_new_groups > 0 && x->pooling != NMC_POOL_PARTIAL)
+    return fail(-1, "predict_set: a new group's values come from the hyper-parameters: "
+                    "partial pooling only");
+  std::vector<nmc_waic_tile> t;
+  for (int64_t i = 0; i < n_new; ++i) {
+    const int g = new_group[i];
+    if (g >= x->G || g < -n_new_groups)
+      return fail(-1, "predict_set: group code " + std::to_string(g) + " of new observation " +
+                          std::to_string(i) + " (training groups 0.." + std::to_string(x->G - 1) +
+                          ", new groups -1..-" + std::to_string(n_new_groups) + ")");
+    if (t.empty() || t.back().g != g || t.back().len == NMC_WAIC_T)
+      t.push_back({i, g, 1});
+    else
+      ++t.back().len;
+  }
+  if (t.size() > (size_t)0x7fffffff - 4) return fail(-1, "predict_set: too many tiles");
+  HIPCHK(hipStreamSynchronize(x->stream));
+  predict_free(x);
+  if (!x->pbad)
+    if (int rc = dalloc(x, &x->pbad, 2)) return rc;
+  if (int rc = dalloc(x, &x->pobs, (size_t)n_new * x->nf)) return rc;
+  if (int rc = dalloc(x, &x->pgrp, (size_t)n_new)) return rc;
+  if (int rc = dalloc(x, &x->ptiles, t.size())) return rc;
+  HIPCHK(hipMemcpy(x->pobs, new_obs, (size_t)n_new * x->nf * 8, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(x->pgrp, new_group, (size_t)n_new * 4, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(x->ptiles, t.data(), t.size() * sizeof(nmc_waic_tile), hipMemcpyHostToDevice));
+  x->n_ptiles = (int)t.size();
+  x->n_pnew = n_new;
+  x->pK = n_new_groups;
+  return 0;
+}
+
+int nmc_predict_draws(nmc_ctx* x, int row_begin, int n_rows, double* yrep, double* ll,
+                      double* theta_new) {
+  RES_PARK(x);
+  hipSetDevice(x->device);
+  if (row_begin < 0 || n_rows < 0 || row_begin > x->d.n_rows - n_rows || n_rows > 65535)
+    return fail(-1, "row range out of bounds (at most 65535 rows per call)");
+  if (x->C > 65535) return fail(-1, "predict_draws: at most 65535 chains per engine");
+  if (x->n_pnew == 0) return fail(-1, "predict_draws: no new table (nmc_predict_set first)");
+  if (yrep)
+    if (int rc = ppc_check(x)) return rc;
+  HIPCHK(hipStreamSynchronize(x->stream));
+  if (int rc = check_timeout(x)) return rc;
+  const size_t cr = (size_t)x->C * n_rows;
+  const size_t ny = yrep ? cr * x->n_pnew * x->nresp : 0, nl = ll ? cr * x->n_pnew : 0;
+  const size_t nt = theta_new ? cr * x->pK * x->P : 0;
+  if (ny + nl + nt == 0) return 0;
+  double* o = nullptr;
+  HIPCHK(hipMalloc(&o, (ny + nl + nt) * 8));
+  NmcCall c;
+  c.op = NMC_OP_PREDICT_DRAWS;
+  c.i0 = row_begin;
+  c.i1 = row_begin + n_rows;
+  c.out = ny ? o : nullptr;
+  c.aux = nl ? o + ny : nullptr;
+  c.aux2 = nt ? o + ny + nl : nullptr;
+  int rc = nmc_call_family(x, c);
+  if (!rc) {
+    hipError_t e = hipSuccess;
+    hipStream_t st = x->stream;
+    if (ny) e = hipMemcpyAsync(yrep, c.out, ny * 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && nl) e = hipMemcpyAsync(ll, c.aux, nl * 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && nt)
+      e = hipMemcpyAsync(theta_new, c.aux2, nt * 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) rc = fail(-2, std::string("predict_draws: ") + hipGetErrorString(e));
+  }
+  hipStreamSynchronize(x->stream);
+  hipFree(o);
+  return rc;
+}
+
+int nmc_predict_partials(nmc_ctx* x, int row_begin, int n_rows, int n_valid, double* dens,
+                         double* state, uint32_t* count, int64_t* nonfinite_draws,
+                         int64_t* nonfinite_ll) {
+  RES_PARK(x);
+  hipSetDevice(x->device);
+  if (row_begin < 0 || n_rows < 1 || row_begin > x->d.n_rows - n_rows)
+    return fail(-1, "row range out of bounds (at least one recorded row)");
+  if (n_rows >= (1 << 26)) return fail(-1, "predict_partials: 2^26 or more rows (uint32 counts)");
+  if (n_valid < 1 || n_valid > x->C) return fail(-1, "n_valid must be in 1..n_chains");
+  if (x->n_pnew == 0) return fail(-1, "predict_partials: no new table (nmc_predict_set first)");
+  if ((state != nullptr) != (count != nullptr))
+    return fail(-1, "predict_partials: state and count come together");
+  if (!dens && !state) return fail(-1, "predict_partials: nothing asked for");
+  if (state)
+    if (int rc = ppc_check(x)) return rc;
+  HIPCHK(hipStreamSynchronize(x->stream));
+  if (int rc = check_timeout(x)) return rc;
+  *nonfinite_draws = 0;
+  *nonfinite_ll = 0;
+  const int CB = x->d.CB, NR = x->nresp;
+  const size_t nn = (size_t)CB * x->n_pnew;
+  const size_t nd = dens ? 2 * nn : 0, ns = state ? 3 * nn * NR : 0, nc = state ? 2 * nn * NR : 0;
+  double* o = nullptr;
+  HIPCHK(hipMalloc(&o, (nd + ns) * 8 + nc * 4 + 8));
+  hipError_t e = hipMemsetAsync(x->pbad, 0, 16, x->stream);
+  NmcCall c;
+  c.op = NMC_OP_PREDICT;
+  c.i0 = row_begin;
+  c.i1 = row_begin + n_rows;
+  c.nc = n_valid;
+  c.aux = nd ? o : nullptr;
+  c.out = ns ? o + nd : nullptr;
+  c.cnt = ns ? (uint32_t*)(o + nd + ns) : nullptr;
+  int rc = e == hipSuccess ? nmc_event_record(x, 16) : 0;
+  if (!rc && e == hipSuccess) rc = nmc_call_family(x, c);
+  if (!rc && e == hipSuccess) rc = nmc_event_record(x, 17);
+  if (!rc) {
+    unsigned long long bad[2] = {0, 0};
+    hipStream_t st = x->stream;
+    if (e == hipSuccess && nd) e = hipMemcpyAsync(dens, c.aux, nd * 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && ns) e = hipMemcpyAsync(state, c.out, ns * 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && nc) e = hipMemcpyAsync(count, c.cnt, nc * 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(bad, x->pbad, 16, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) rc = fail(-2, std::string("predict_partials: ") + hipGetErrorString(e));
+    *nonfinite_draws = (int64_t)bad[0];
+    *nonfinite_ll = (int64_t)bad[1];
   }
   hipStreamSynchronize(x->stream);
   hipFree(o);

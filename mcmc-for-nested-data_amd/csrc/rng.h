@@ -26,6 +26,8 @@ enum {
   NMC_PURPOSE_HYPER_NORMAL = 2,
   NMC_PURPOSE_GAMMA_BOOST = 3,
   NMC_PURPOSE_PREDICT = 4,   // posterior predictive draws (ppc.h): counter (row, obs, field, 4)
+  NMC_PURPOSE_NEW_GROUP = 5,     // a new group's theta (predict.h): counter (row, new group, param, 5)
+  NMC_PURPOSE_PREDICT_NEW = 6,   // draws for new observations (predict.h): (row, new obs, field, 6)
   NMC_PURPOSE_GAMMA_BASE = 16,
   NMC_GAMMA_MAX_ATTEMPTS = 64
 };

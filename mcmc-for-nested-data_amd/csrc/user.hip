@@ -27,10 +27,12 @@ namespace {
 // kernel table entries, in name-expression order
 // (nmc_k_run: mode m (0..4) with rows in LDS at UK_RUN0 + m, rows staged at UK_RUN0 + 5 + m;
 // the half layout at UK_HALF; WAIC's reduction, waic.h, at UK_WAIC; the LL in store layout of
-// PSIS-LOO, ll_kernels.h, at UK_LOO_LL; the posterior predictive kernels, ppc.h, at UK_PPC_*)
+// PSIS-LOO, ll_kernels.h, at UK_LOO_LL; the posterior predictive kernels, ppc.h, at UK_PPC_*;
+// the kernels of predict.h at UK_PREDICT and UK_PREDICT_DRAWS)
 enum { UK_RUN0 = 0, UK_NRUN = 5, UK_GROUP_LL = 10, UK_OBS_LL_ROWS = 11, UK_OBS_LL = 12,
        UK_GROUP_LL_RL = 13, UK_GROUP_FIN = 14, UK_HALF = 15, UK_WAIC = 16, UK_LOO_LL = 17,
-       UK_PPC_DRAWS = 18, UK_PPC_OBS = 19, UK_PPC_GROUP = 20, UK_N = 21 };
+       UK_PPC_DRAWS = 18, UK_PPC_OBS = 19, UK_PPC_GROUP = 20, UK_PREDICT = 21,
+       UK_PREDICT_DRAWS = 22, UK_N = 23 };
 const char* const kNames[UK_N] = {
     "nmc_k_run<FamUser, 0, true>", "nmc_k_run<FamUser, 1, true>", "nmc_k_run<FamUser, 2, true>",
     "nmc_k_run<FamUser, 3, true>", "nmc_k_run<FamUser, 4, true>",
@@ -40,7 +42,8 @@ const char* const kNames[UK_N] = {
     "nmc_k_group_part<FamUser, false>", "nmc_k_obs_ll_rows<FamUser>",
     "nmc_k_obs_ll<FamUser>", "nmc_k_group_part<FamUser, true>", "nmc_k_group_fin<FamUser>",
     "nmc_k_run<FamUser, 6, true>", "nmc_k_waic<FamUser>", "nmc_k_loo_ll<FamUser>",
-    "nmc_k_ppc_draws<FamUser>", "nmc_k_ppc_obs<FamUser>", "nmc_k_ppc_group<FamUser>"};
+    "nmc_k_ppc_draws<FamUser>", "nmc_k_ppc_obs<FamUser>", "nmc_k_ppc_group<FamUser>",
+    "nmc_k_predict<FamUser>", "nmc_k_predict_draws<FamUser>"};
 int run_index(const nmc_ctx* x, int mode) {
   if (mode == NMC_MODE_HALF) return UK_HALF;
   return UK_RUN0 + mode + (x->d.rows_lds ? 0 : UK_NRUN);
@@ -333,6 +336,43 @@ int nmc_call_user(nmc_ctx* x, NmcCall& c) {
       if (int rc = user_fn(x, UK_PPC_GROUP, &f)) return rc;
       return launch(x, f, dim3((unsigned)x->G, (unsigned)d0.CB, (unsigned)c.nb), dim3(256), 0,
                     args);
+    }
+    case NMC_OP_PREDICT: {
+      if (x->n_ptiles == 0) return 0;
+      Dev dd = d0;
+      const double* nobs = x->pobs;
+      const nmc_waic_tile* tiles = x->ptiles;
+      int ntiles = x->n_ptiles;
+      int64_t n_new = x->n_pnew;
+      int pc = x->pooling == NMC_POOL_PARTIAL ? 2 : 0, row0 = c.i0, nrows = c.i1 - c.i0;
+      int n_valid = c.nc;
+      double* dens = c.aux;
+      double* st = c.out;
+      uint32_t* cnt = c.cnt;
+      unsigned long long* bad = x->pbad;
+      void* args[] = {&dd, &fam, (void*)&nobs, (void*)&tiles, &ntiles, &n_new, &pc, &row0,
+                      &nrows, &n_valid, &dens, &st, &cnt, &bad};
+      if (int rc = user_fn(x, UK_PREDICT, &f)) return rc;
+      return launch(x, f, dim3((unsigned)((x->n_ptiles + 3) / 4), (unsigned)d0.CB), dim3(256),
+                    0, args);
+    }
+    case NMC_OP_PREDICT_DRAWS: {
+      const int n = c.i1 - c.i0;
+      const int64_t slots = std::max<int64_t>(x->n_pnew, x->pK);
+      if (n <= 0 || slots == 0) return 0;
+      Dev dd = d0;
+      const double* nobs = x->pobs;
+      const int* ngrp = x->pgrp;
+      int64_t n_new = x->n_pnew;
+      int K = x->pK, pc = x->pooling == NMC_POOL_PARTIAL ? 2 : 0, row0 = c.i0, nrows = n;
+      double* yrep = c.out;
+      double* ll = c.aux;
+      double* thn = c.aux2;
+      void* args[] = {&dd, &fam, (void*)&nobs, (void*)&ngrp, &n_new, &K, &pc, &row0, &nrows,
+                      &yrep, &ll, &thn};
+      if (int rc = user_fn(x, UK_PREDICT_DRAWS, &f)) return rc;
+      return launch(x, f, dim3((unsigned)((slots + 255) / 256), (unsigned)x->C, (unsigned)n),
+                    dim3(256), 0, args);
     }
     case NMC_OP_LOO_LL: {
       int nrows = c.i1 - c.i0, nb = c.nb;

@@ -8,5 +8,6 @@ sampleDiagnosis.diagnoseSamples reads them unchanged.
 
 from .data import example_distribution, example_regression, linreg, logistic  # noqa: F401
 from .families import GaussianMean, LinearRegression, Logistic, is_family  # noqa: F401
+from .predict import NewData  # noqa: F401
 
 __version__ = "0.1.0"

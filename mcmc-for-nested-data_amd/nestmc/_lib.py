@@ -71,6 +71,13 @@ SIGNATURES = {
     "nmc_ppc_partials": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                         _c_double_p, _c_uint32_p, _c_double_p, _c_uint32_p,
                                         _c_double_p, _c_int64_p]),
+    "nmc_predict_set": (ctypes.c_int, [_vp, _c_double_p, ctypes.c_int64, ctypes.c_int, _c_int32_p,
+                                       ctypes.c_int]),
+    "nmc_predict_draws": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _c_double_p,
+                                         _c_double_p, _c_double_p]),
+    "nmc_predict_partials": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                            _c_double_p, _c_double_p, _c_uint32_p, _c_int64_p,
+                                            _c_int64_p]),
     "nmc_conv_partials": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                          _c_double_p, _c_double_p, _c_double_p]),
     "nmc_summary": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,

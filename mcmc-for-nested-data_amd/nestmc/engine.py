@@ -316,6 +316,94 @@ class Engine:
         parts = self.ppc_partials(row_begin, n_rows, n_valid)
         return _ppc.finish(_ppc.merge(parts), self.off, self.observed())
 
+    # -- held-out rows and new groups (nestmc.predict; csrc/predict.h) ----------------------
+    def set_new_data(self, new_data):
+        """The table to predict for (a nestmc.predict.NewData; None clears it): checked
+        against the family and the pooling (ValueError), then copied to the device
+        (nmc_predict_set)."""
+        if new_data is None:
+            check(self.lib.nmc_predict_set(self.h, None, 0, 0, None, 0))
+            self.new_data = None
+            return
+        new_data.check(self.family, self.G, self.pooling)
+        check(self.lib.nmc_predict_set(
+            self.h, dptr(new_data.obs), new_data.n_new, new_data.n_fields,
+            new_data.group.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), new_data.K))
+        self.new_data = new_data
+
+    def _new_data(self):
+        nd = getattr(self, "new_data", None)
+        if nd is None:
+            raise ValueError("no new table: set_new_data(NewData(obs, group)) first")
+        return nd
+
+    def predict_draws(self, row_begin=0, n_rows=None, yrep=True, ll=True, theta_new=True):
+        """At recorded rows of the sample store, for the new table (nmc_predict_draws): a dict
+        of yrep [C, rows, n_new, NRESP] (the draws), ll [C, rows, n_new] (the log density of
+        every new row) and theta_new [C, rows, K, P] (the new groups' values); an array not
+        asked for is None.  For small windows, tests and statistics of one's own --
+        Engine.predict never forms them.  yrep needs a family that can draw."""
+        nd = self._new_data()
+        if n_rows is None:
+            n_rows = self.n_rows - row_begin
+        n_rows = max(int(n_rows), 0)
+        NR = self.n_resp()
+        y = numpy.empty((self.C, n_rows, nd.n_new, max(NR, 1))) if yrep else None
+        L = numpy.empty((self.C, n_rows, nd.n_new)) if ll else None
+        t = numpy.empty((self.C, n_rows, nd.K, self.P)) if theta_new else None
+        check(self.lib.nmc_predict_draws(self.h, int(row_begin), n_rows, dptr(y), dptr(L),
+                                         dptr(t)))
+        return dict(yrep=y, ll=L, theta_new=t)
+
+    def predict_partials_raw(self, row_begin=0, n_rows=None, n_valid=None):
+        """nmc_predict_partials as it answers: (the chain blocks' partials, a list of
+        nestmc.predict dicts in chain-block order, each with zero non-finite counts; the
+        call's (non-finite draws, non-finite ll terms)).  A family that cannot draw gets the
+        density alone (NRESP = 0 in the partials)."""
+        nd = self._new_data()
+        if n_rows is None:
+            n_rows = self.n_rows - row_begin
+        if n_valid is None:
+            n_valid = self.C
+        CB, n, NR = (self.C + 63) // 64, nd.n_new, self.n_resp()
+        dens = numpy.empty((CB, 2, n))
+        st = numpy.empty((CB, 3, NR, n))
+        ct = numpy.zeros((CB, 2, NR, n), dtype=numpy.uint32)
+        bd, bl = ctypes.c_int64(), ctypes.c_int64()
+        check(self.lib.nmc_predict_partials(
+            self.h, int(row_begin), int(n_rows), int(n_valid), dptr(dens),
+            dptr(st) if NR else None,
+            ct.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)) if NR else None,
+            ctypes.byref(bd), ctypes.byref(bl)))
+        parts = []
+        for b in range(CB):
+            ns = float(int(n_rows) * min(64, max(0, int(n_valid) - 64 * b)))
+            parts.append(dict(dens=numpy.concatenate([dens[b], numpy.full((1, n), ns)]),
+                              state=st[b], count=ct[b].astype(numpy.int64),
+                              nonfinite_draws=0, nonfinite_ll=0))
+        return parts, (bd.value, bl.value)
+
+    def predict_partials(self, row_begin=0, n_rows=None, n_valid=None):
+        """The prediction partials of every chain block over recorded rows [row_begin,
+        row_begin + n_rows) and local chains [0, n_valid), reduced on the device from the
+        sample store (nmc_predict_partials; nestmc.predict): a list of dicts in chain-block
+        order.  Chains from n_valid on (padding) enter as the identity.  A draw that is not
+        finite, or a log density that is not finite at a row with a response, is an error."""
+        parts, bad = self.predict_partials_raw(row_begin, n_rows, n_valid)
+        self.predict_nonfinite = bad
+        if bad[0] or bad[1]:
+            raise _lib.NestmcError("prediction: %d draws and %d log densities were not finite"
+                                   % bad)
+        return parts
+
+    def predict(self, row_begin=0, n_rows=None, n_valid=None):
+        """The PredictionResult (nestmc.predict) of this engine's chains for the new table: its
+        chain blocks' partials merged in chain-block order."""
+        from . import predict as _predict
+        parts = self.predict_partials(row_begin, n_rows, n_valid)
+        return _predict.finish(_predict.merge(parts), self._new_data(),
+                               self.family.response_fields())
+
     def loo_raw(self, row_begin=0, n_rows=None, n_valid=None, obs_batch=0):
         """PSIS-LOO's per-observation results over recorded rows [row_begin, row_begin +
         n_rows) and local chains [0, n_valid), computed on the device from the sample store

@@ -30,6 +30,7 @@ from . import summary as _summary
 from . import loo as _loo
 from . import rankdiag as _rankdiag
 from . import ppc as _ppc
+from . import predict as _predict
 from . import waic as _waic
 from .engine import Engine
 from .families import is_family
@@ -72,7 +73,7 @@ def sample_posterior(nChains, nIter, nSamples, parameterName, nGroups, nResponse
                      computeWaic=False, computeDiagnostics=False, computeSummary=False,
                      computeLoo=False, computeRankDiagnostics=False,
                      computeGroupComparison=False, computeCorrelation=False,
-                     computePredictiveChecks=False):
+                     computePredictiveChecks=False, predictFor=None):
     """Drop-in for posteriorSampling.samplePosterior (same positional/keyword API).
 
     Extra keyword-only options (all optional):
@@ -166,6 +167,20 @@ def sample_posterior(nChains, nIter, nSamples, parameterName, nGroups, nResponse
                  ranks (merged in engine and rank order: counts exactly, moments by Chan's
                  update).  A family that cannot draw (a DeviceLikelihood without
                  nmc_user_predict) raises ValueError before sampling starts
+      predictFor  a nestmc.NewData(obs, group): rows the model was not fitted to, in the
+                 family's row layout, each with a group code -- g >= 0 a training group,
+                 -(k + 1) new group k, a group the model has never seen, whose values are drawn
+                 from every sample's hyper-parameters (pooling="partial" only).  After the loop
+                 the GPU evaluates, from the device sample store, per new row the predictive
+                 mean and sd and, where the row's response is given (not NaN), its PIT and the
+                 log predictive density of the held-out value (nestmc.predict; the draws never
+                 leave the device): outputDirectory/prediction_pointwise.csv and
+                 prediction_groups.csv, "predictions" (a nestmc.predict.PredictionResult) in
+                 the returned dict and one log line with elpd_test and its standard error.
+                 Any number of engines and ranks, merged as the predictive checks are.  A
+                 DeviceLikelihood without nmc_user_predict gets the density alone.  A table of
+                 another width, a group code beyond the training groups or a new group without
+                 partial pooling raises ValueError before sampling starts
     nProcesses sizes the host threads used for chain initialisation and CSV writing.
     """
     start_time = datetime.datetime.now()
@@ -201,6 +216,10 @@ def sample_posterior(nChains, nIter, nSamples, parameterName, nGroups, nResponse
         raise ValueError("computePredictiveChecks needs a family that can draw from its "
                          "likelihood: this DeviceLikelihood's source does not define "
                          "nmc_user_predict (INTEGRATION.md, 'Posterior predictive checks')")
+    if predictFor is not None:
+        if not isinstance(predictFor, _predict.NewData):
+            raise ValueError("predictFor must be a nestmc.NewData(obs, group)")
+        predictFor.check(logLikelihoodFunction, 1 if pooling == "complete" else nGroups, pooling)
     names = tuple(parameterName)
     if len(names) != logLikelihoodFunction.n_params:
         raise ValueError("parameterName has %d names, the likelihood family has %d parameters"
@@ -250,6 +269,8 @@ def sample_posterior(nChains, nIter, nSamples, parameterName, nGroups, nResponse
         raise ValueError("computeLoo needs at least two samples")
     if computePredictiveChecks and len(record_iterations(nIter, burn, thin)) * nChains < 2:
         raise ValueError("computePredictiveChecks needs at least two samples")
+    if predictFor is not None and len(record_iterations(nIter, burn, thin)) * nChains < 2:
+        raise ValueError("predictFor needs at least two samples")
     if computeCorrelation:
         n_val = len(record_iterations(nIter, burn, thin)) * \
             (nChains if chains is None else len(chains))
@@ -294,7 +315,7 @@ def sample_posterior(nChains, nIter, nSamples, parameterName, nGroups, nResponse
                   computeSummary=computeSummary,
                   computeGroupComparison=computeGroupComparison,
                   computeCorrelation=computeCorrelation,
-                  computePredictiveChecks=computePredictiveChecks)
+                  computePredictiveChecks=computePredictiveChecks, predictFor=predictFor)
         res = ranks.run_per_device(kw, devices)
         _finish_log(logger, [], start_time, displayProgress)
         return res
@@ -378,7 +399,7 @@ def sample_posterior(nChains, nIter, nSamples, parameterName, nGroups, nResponse
                             compute_rank=bool(computeRankDiagnostics),
                             compute_group=bool(computeGroupComparison),
                             compute_corr=bool(computeCorrelation),
-                            compute_ppc=bool(computePredictiveChecks))
+                            compute_ppc=bool(computePredictiveChecks), predict_for=predictFor)
     finally:
         for eng, _, _ in engines:
             eng.close()
@@ -470,6 +491,35 @@ def _ppc_of(engines, rank_info, n_real):
         raise _lib.NestmcError("posterior predictive checks: %d draws were not finite"
                                % part["nonfinite"])
     return _ppc.finish(part, eng0.off, eng0.observed())
+
+
+def _predict_of(engines, rank_info, n_real, new_data):
+    """predictFor: every engine's chain-block partials for the new table over all recorded rows
+    (its padding chains, ids >= n_real, as the identity), merged in engine order; the ranks of
+    process_per_device send theirs over the host group and rank 0 merges them in rank order and
+    finishes (the other ranks: None).  A draw or a held-out log density that is not finite is an
+    error."""
+    eng0 = engines[0][0]
+    parts = []
+    for eng, _, ids in engines:
+        n_valid = sum(1 for c in ids if c < n_real)
+        if n_valid > 0:
+            eng.set_new_data(new_data)
+            blocks, bad = eng.predict_partials_raw(n_valid=n_valid)
+            blocks[0]["nonfinite_draws"], blocks[0]["nonfinite_ll"] = bad
+            parts.extend(blocks)
+        else:
+            parts.append(_predict.identity(new_data.n_new, eng.n_resp()))
+    part = _predict.merge(parts)
+    if rank_info is not None:
+        got = rank_info["hg"].gather(_predict.pack(part))
+        if rank_info["rank"] != 0:
+            return None
+        part = _predict.merge_ranks([_predict.unpack(b) for b in got])
+    if part["nonfinite_draws"] or part["nonfinite_ll"]:
+        raise _lib.NestmcError("prediction: %d draws and %d log densities were not finite"
+                               % (part["nonfinite_draws"], part["nonfinite_ll"]))
+    return _predict.finish(part, new_data, eng0.family.response_fields())
 
 
 def _conv_of(engines, rank_info, n_real, header):
@@ -596,7 +646,8 @@ def _sample_loop(engines, nIter, burn, thin, names, G, partial, saveLogLikelihoo
                  sample_dir, threads, displayProgress, return_samples, logger, chain_logs,
                  start_time, rank_info=None, compute_waic=False, waic_dir=None,
                  n_real=None, compute_conv=False, compute_summary=False, compute_loo=False,
-                 compute_rank=False, compute_group=False, compute_corr=False, compute_ppc=False):
+                 compute_rank=False, compute_group=False, compute_corr=False, compute_ppc=False,
+                 predict_for=None):
     """The device loop, the per-observation LL rows and the sample files of
     sample_posterior (the caller closes the engines whatever happens here).  rank_info: a
     rank of process_per_device -- this rank writes its chains' logLikelihood files, rank 0
@@ -684,6 +735,20 @@ def _sample_loop(engines, nIter, burn, thin, names, G, partial, saveLogLikelihoo
                     logger.warning(warn)
                 if displayProgress:
                     output.print_progress(warn)
+    predict_result = None
+    if predict_for is not None:
+        predict_result = _predict_of(engines, rank_info, n_real, predict_for)
+        if predict_result is not None:
+            if write_files:
+                _predict.write_csvs(predict_result, waic_dir)
+            line = ("Prediction for %d new observations (%d with a held-out response, %d new "
+                    "groups): elpd_test = %.6g +- %.3g."
+                    % (predict_result.n_new, predict_result.n_response, predict_for.K,
+                       predict_result.elpd_test, predict_result.se))
+            if logger:
+                logger.info(line)
+            if displayProgress:
+                output.print_progress(line)
     summary_result = None
     if compute_summary:
         summary_result = _summary_of(engines, rank_info, n_real, header)
@@ -734,6 +799,8 @@ def _sample_loop(engines, nIter, burn, thin, names, G, partial, saveLogLikelihoo
             res["correlation"] = corr_result
         if ppc_result is not None:
             res["predictive_checks"] = ppc_result
+        if predict_result is not None:
+            res["predictions"] = predict_result
         if summary_result is not None:
             res["summary"] = summary_result
             if conv_result is not None:

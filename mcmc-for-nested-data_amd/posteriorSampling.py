@@ -27,7 +27,7 @@ def samplePosterior(nChains, nIter, nSamples,
                     computeWaic=False, computeDiagnostics=False, computeSummary=False,
                     computeLoo=False, computeRankDiagnostics=False,
                     computeGroupComparison=False, computeCorrelation=False,
-                    computePredictiveChecks=False, **gpu_options):
+                    computePredictiveChecks=False, predictFor=None, **gpu_options):
     """Sample the posterior of a nested model; samples go to outputDirectory/sample/.
 
     Arguments mirror the reference (posteriorSampling.py:28-145).  Keyword-only
@@ -51,7 +51,10 @@ def samplePosterior(nChains, nIter, nSamples,
     number of engines.  computePredictiveChecks=True also draws a replicated data set from
     every recorded sample on the GPU and compares it with the observed data, per observation
     and per group (ppc_groups.csv, ppc_pointwise.csv; nestmc.ppc) -- a built-in family or a
-    DeviceLikelihood with nmc_user_predict, any number of engines.  Returns None like the reference unless return_samples=True.
+    DeviceLikelihood with nmc_user_predict, any number of engines.  predictFor=nestmc.NewData(
+    obs, group) also predicts rows the model was not fitted to, of training groups and of
+    groups it has never seen, on the GPU (prediction_pointwise.csv, prediction_groups.csv;
+    nestmc.predict).  Returns None like the reference unless return_samples=True.
     """
     return sample_posterior(nChains, nIter, nSamples, parameterName, nGroups,
                             nResponsesPerGroup, pooling, logLikelihoodFunction,
@@ -65,4 +68,5 @@ def samplePosterior(nChains, nIter, nSamples,
                             computeRankDiagnostics=computeRankDiagnostics,
                             computeGroupComparison=computeGroupComparison,
                             computeCorrelation=computeCorrelation,
-                            computePredictiveChecks=computePredictiveChecks, **gpu_options)
+                            computePredictiveChecks=computePredictiveChecks,
+                            predictFor=predictFor, **gpu_options)
