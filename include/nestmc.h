@@ -513,6 +513,16 @@ int nmc_debug_rng(const uint32_t* ctr5, int n, uint32_t seed, double gamma_shape
  * host (on_device = 0, no GPU needed) or by a device kernel (on_device = 1); the two are
  * bit-identical by construction (IEEE add / mul / fma / div, rint, ldexp only).          */
 int nmc_debug_softplus(const double* x, int n, double* out, int on_device);
+/* The variate math of csrc/rng.h on caller inputs, on the host (on_device = 0, no GPU needed)
+ * or by a device kernel: which = 0 nmc_log_unit(a[i]), 1 nmc_cos2pi(a[i]), 2
+ * nmc_box_muller(a[i], b[i]) (b is read for which = 2 only, but must hold n doubles).  IEEE
+ * add / mul / fma / div, sqrt and frexp only, so the two are bit-identical.                */
+int nmc_debug_varmath(int which, const double* a, const double* b, int n, double* out,
+                      int on_device);
+/* nmc_debug_igamci's host form (no GPU needed): the same code with libm's log / exp / pow /
+ * lgamma, so it agrees with the device to rounding, not bit for bit.                       */
+int nmc_debug_igamci_host(const double* a, const double* q, const double* lga, int n,
+                          double* out);
 /* The inverse of nmc_get_samples: writes recorded rows [row_begin, row_begin+n_rows) of the
  * device sample store from in[row][col][C] (the store as set_schedule sized it; no sampling
  * needed), so that the store's consumers -- nmc_obs_ll_rows, nmc_write_ll_csvs,

@@ -114,6 +114,18 @@ __global__ void nmc_k_debug_rng(const uint32_t* ctr, int n, uint32_t seed, doubl
   out[4 * i + 3] = nmc_gamma_mt(ga, k[0], k[2], k[4], seed);
 }
 
+// rng.h's variate math on the caller's arguments, host and device (nmc_debug_varmath):
+// which = 0 nmc_log_unit(a), 1 nmc_cos2pi(a), 2 nmc_box_muller(a, b)
+NMC_HD double nmc_varmath_eval(int which, double a, double b) {
+  return which == 0 ? nmc_log_unit(a) : which == 1 ? nmc_cos2pi(a) : nmc_box_muller(a, b);
+}
+
+__global__ void nmc_k_debug_varmath(int which, const double* a, const double* b, int n,
+                                    double* out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = nmc_varmath_eval(which, a[i], b[i]);
+}
+
 __global__ void nmc_k_debug_softplus(const double* x, int n, double* out) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) out[i] = nmc_softplus(x[i]);

@@ -2964,6 +2964,38 @@ int nmc_debug_igamci(const double* a, const double* q, const double* lga, int n,
   return 0;
 }
 
+int nmc_debug_igamci_host(const double* a, const double* q, const double* lga, int n,
+                          double* out) {
+  if (n < 0) return fail(-1, "n < 0");
+  for (int i = 0; i < n; ++i) out[i] = nmc_igamci(a[i], q[i], lga[i]);
+  return 0;
+}
+
+int nmc_debug_varmath(int which, const double* a, const double* b, int n, double* out,
+                      int on_device) {
+  if (n < 0) return fail(-1, "n < 0");
+  if (which < 0 || which > 2) return fail(-1, "which must be 0 (log), 1 (cos) or 2 (Box-Muller)");
+  if (!on_device) {
+    for (int i = 0; i < n; ++i) out[i] = nmc_varmath_eval(which, a[i], b[i]);
+    return 0;
+  }
+  double *da, *db, *dout;
+  const size_t bytes = (size_t)(n ? n : 1) * 8;
+  HIPCHK(hipMalloc(&da, bytes));
+  HIPCHK(hipMalloc(&db, bytes));
+  HIPCHK(hipMalloc(&dout, bytes));
+  HIPCHK(hipMemcpy(da, a, (size_t)n * 8, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(db, b, (size_t)n * 8, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(nmc_k_debug_varmath, dim3((n + 255) / 256 > 0 ? (n + 255) / 256 : 1),
+                     dim3(256), 0, 0, which, (const double*)da, (const double*)db, n, dout);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpy(out, dout, (size_t)n * 8, hipMemcpyDeviceToHost));
+  hipFree(da);
+  hipFree(db);
+  hipFree(dout);
+  return 0;
+}
+
 int nmc_debug_rng(const uint32_t* ctr5, int n, uint32_t seed, double gamma_shape, double* out4) {
   uint32_t* dc;
   double* dout;

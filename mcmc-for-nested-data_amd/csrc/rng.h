@@ -67,14 +67,17 @@ NMC_HD nmc_d2 nmc_uniform2(uint32_t it, uint32_t group, uint32_t param, uint32_t
 // the library's fp64 log and cos cost 76 and 109 fp64 instructions on gfx950 (double-
 // double evaluation; cos also carries a Payne-Hanek reduction for large arguments), which
 // made every step variate 291 fp64 instructions and the fill 0.58 us per cfg-3 iteration
-// (profiles/r05/r05c_fillbench.json).  Both below are within ~1 ulp of the exact value
-// (tools/varmath_check.hip), like the library's; the oracle keeps numpy's log and cos
-// (tests compare at rtol 1e-14).
+// (profiles/r05/r05c_fillbench.json).  Both below are within 2.4 ulp (4.8 x 2^-53 relative) of
+// the exact value; measured against 200-bit references, in units of 2^-53 relative: log 2.39,
+// cos 2.28, cos where |cos| < 1e-3 1.28, Box-Muller 3.64 of the 9.2 that follows; the zeros at
+// log(1), cos2pi(1/4) and cos2pi(3/4) are exact (tests/test_varmath_host.py on the host form;
+// tests/test_gpu_varmath.py: the device returns the host's bits).  The oracle keeps numpy's
+// log and cos (tests compare at rtol 1e-14).
 //
-// log(x) for x in [0, 1]: x = m 2^e with m in [sqrt(1/2), sqrt(2)) (frexp, exact), log(m) =
-// 2 atanh(s), s = (m - 1) / (m + 1), |s| <= 0.1716 (m - 1 exact: Sterbenz), the series to
-// s^23 (the first omitted term < 1e-18 relative); e ln 2 in two parts (ln2_hi has 32
-// significant bits, so e * ln2_hi is exact).  0 -> -inf, NaN propagates.
+// log(x) for x in [0, 1], denormals included: x = m 2^e with m in [sqrt(1/2), sqrt(2))
+// (frexp, exact), log(m) = 2 atanh(s), s = (m - 1) / (m + 1), |s| <= 0.1716 (m - 1 exact:
+// Sterbenz), the series to s^23 (the first omitted term < 1e-18 relative); e ln 2 in two
+// parts (ln2_hi has 32 significant bits, so e * ln2_hi is exact).  0 -> -inf, NaN propagates.
 NMC_HD double nmc_log_unit(double x) {
   int e = 0;
   double m = frexp(x, &e);                       // m in [0.5, 1)

@@ -22,7 +22,7 @@
 #define NMC_LOG_PI 1.1447298858494002
 #define NMC_LN2 0.6931471805599453
 
-__device__ __forceinline__ double nmc_nan() { return __builtin_nan(""); }
+__host__ __device__ __forceinline__ double nmc_nan() { return __builtin_nan(""); }
 
 // norm.logpdf with log(scale) precomputed by the caller (lsd = log(scale)).
 __device__ __forceinline__ double nmc_norm_logpdf(double x, double loc, double scale,
@@ -133,8 +133,12 @@ __device__ __forceinline__ double nmc_pairwise_sum(const Get& get, int n) {
 // ---------------------------------------------------------------------------
 // regularised incomplete gamma and its inverse (replay mode: the reference's U)
 // ---------------------------------------------------------------------------
+// Host and device (the host form is nmc_debug_igamci_host's, for tests without a GPU): the
+// host evaluates log / exp / pow / lgamma with libm, the device with its own library, so the
+// two agree to rounding, not bit for bit; each is within 1e-12 of the exact root for shapes
+// 0.5 ... 512 (tests/test_varmath_host.py, tests/test_gpu_varmath.py).
 // P(a,x), Q(a,x): series for x < a+1, Lentz continued fraction otherwise.
-__device__ inline void nmc_gamma_pq(double a, double x, double lga, double* P, double* Q) {
+__host__ __device__ inline void nmc_gamma_pq(double a, double x, double lga, double* P, double* Q) {
   if (!(x > 0.0)) { *P = 0.0; *Q = 1.0; return; }
   if (isinf(x)) { *P = 1.0; *Q = 0.0; return; }
   const double lpre = a * log(x) - x - lga;
@@ -171,7 +175,7 @@ __device__ inline void nmc_gamma_pq(double a, double x, double lga, double* P, d
 }
 
 // Acklam's inverse normal CDF (|rel err| < 1.2e-9): initial guess only.
-__device__ inline double nmc_ndtri_approx(double p) {
+__host__ __device__ inline double nmc_ndtri_approx(double p) {
   const double a1 = -3.969683028665376e+01, a2 = 2.209460984245205e+02,
                a3 = -2.759285104469687e+02, a4 = 1.383577518672690e+02,
                a5 = -3.066479806614716e+01, a6 = 2.506628277459239e+00;
@@ -200,7 +204,7 @@ __device__ inline double nmc_ndtri_approx(double p) {
 
 // x such that Q(a, x) = q (scipy.special.gammainccinv).  Safeguarded Halley on
 // whichever of P = 1-q / Q = q is the smaller tail, bracketed, to full precision.
-__device__ inline double nmc_igamci(double a, double q, double lga) {
+__host__ __device__ inline double nmc_igamci(double a, double q, double lga) {
   if (isnan(q) || isnan(a) || !(a > 0.0) || q < 0.0 || q > 1.0) return nmc_nan();
   if (q == 0.0) return __builtin_inf();
   if (q == 1.0) return 0.0;

@@ -151,6 +151,10 @@ SIGNATURES = {
     "nmc_debug_stamps": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64)]),
     "nmc_debug_softplus": (ctypes.c_int, [_c_double_p, ctypes.c_int, _c_double_p,
                                           ctypes.c_int]),
+    "nmc_debug_varmath": (ctypes.c_int, [ctypes.c_int, _c_double_p, _c_double_p, ctypes.c_int,
+                                         _c_double_p, ctypes.c_int]),
+    "nmc_debug_igamci_host": (ctypes.c_int, [_c_double_p, _c_double_p, _c_double_p, ctypes.c_int,
+                                             _c_double_p]),
 }
 
 _lib = None

@@ -66,8 +66,12 @@ def uniforms(it, group, param, purpose, chain, seed):
 
 def cos2pi(u):
     """cos(2 pi u), u in [0, 1), with the argument reduced exactly in u (every difference is
-    exact, Sterbenz) to t in [0, 1/8] before numpy's sin / cos of 2 pi t: within ~1 ulp of the
-    exact value everywhere, where cos(fl(2 pi u)) is off by up to ~3000 ulp near the zeros.
+    exact, Sterbenz) to t in [0, 1/8] before numpy's sin / cos of 2 pi t, where cos(fl(2 pi u))
+    is off by up to ~3000 ulp near the zeros.  What remains, in units of 2^-53 relative: the
+    rounded constant and the rounded product 2 pi t (1 each, through a condition number of at
+    most 1 on [0, pi/4]) and the library's sin / cos (below 1 ulp = 2 units), 4 in all, the zeros
+    at 1/4 and 3/4 exact; measured 2.14 against 200-bit mpmath, near the zeros included
+    (tests/test_varmath_host.py::test_oracle_cos2pi_against_mpmath asserts the 4).
     The same function as csrc/rng.h nmc_cos2pi (which evaluates the last step with its own
     polynomials; the two agree to a few ulp)."""
     u = numpy.asarray(u, dtype=numpy.float64)
@@ -90,14 +94,23 @@ def normal(it, group, param, purpose, chain, seed):
     return box_muller(ua, ub)
 
 
-def gamma_mt(a, it, param, chain, seed):
+def gamma_mt(a, it, param, chain, seed, return_attempts=False):
     """Gamma(a, 1) by Marsaglia-Tsang on the hyper gamma purposes (vector over chains).
 
     Restates ``nmc_gamma_mt`` of csrc/rng.h step by step (same squeeze test, same
     attempt counters) so oracle and device accept on the same attempt.
+
+    ``return_attempts``: also return, per draw, the attempt k that accepted (-1: none) and the
+    decision margin: over every attempt the draw went through, the smallest distance of a
+    comparison from its threshold -- v from 0, and where v > 0 the squeeze test's u from
+    1 - 0.0331 z^4 and the log test's log u from its right-hand side.  A draw whose margin
+    exceeds the difference between two evaluations of these quantities takes the same attempt
+    in both.
     """
     chain = numpy.asarray(chain)
     out = numpy.full(chain.shape, numpy.nan)
+    attempt = numpy.full(chain.shape, -1)
+    margin = numpy.full(chain.shape, numpy.inf)
     boost = a < 1.0
     aa = a + 1.0 if boost else a
     d = aa - 1.0 / 3.0
@@ -111,10 +124,16 @@ def gamma_mt(a, it, param, chain, seed):
         v3 = v * v * v
         with numpy.errstate(divide="ignore", invalid="ignore"):
             z2 = z * z
-            acc = ok & ((u < 1.0 - 0.0331 * (z2 * z2)) |
-                        (numpy.log(u) < 0.5 * z2 + d * (1.0 - v3 + numpy.log(v3))))
+            squeeze = 1.0 - 0.0331 * (z2 * z2)
+            rhs = 0.5 * z2 + d * (1.0 - v3 + numpy.log(v3))
+            acc = ok & ((u < squeeze) | (numpy.log(u) < rhs))
+            m = numpy.where(ok, numpy.minimum(numpy.abs(u - squeeze),
+                                              numpy.abs(numpy.log(u) - rhs)), numpy.inf)
+        m = numpy.minimum(m, numpy.abs(v))
+        margin = numpy.where(todo, numpy.minimum(margin, m), margin)
         take = todo & acc
         out[take] = (d * v3)[take]
+        attempt[take] = k
         todo &= ~acc
         if not todo.any():
             break
@@ -122,4 +141,6 @@ def gamma_mt(a, it, param, chain, seed):
     if boost:
         ub, _ = uniforms(it, 0, param, PURPOSE_GAMMA_BOOST, chain, seed)
         out = out * numpy.exp(numpy.log(1.0 - ub) / a)
+    if return_attempts:
+        return out, attempt, margin
     return out
