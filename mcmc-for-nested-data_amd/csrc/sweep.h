@@ -4,7 +4,8 @@
 // sweep_gibbs.h.
 //
 // Same work, tile partition, summation orders, variates and outputs as nmc_k_run
-// (step.h) -- the two are bit-identical and the tests compare them -- built around what
+// (step.h) -- the two are bit-identical and tests/test_gpu_sweep.py compares them, on every
+// instantiation that can be chosen -- built around what
 // MI355X measurements say bounds the loop (profiles/r04_fp64issue.jsonl): one wave issues an
 // fp64 VALU instruction at most every ~5.8 cycles, two waves on a SIMD every ~4.7, three
 // every ~4.5 (the paired row loop with its LDS reads: 7.0 / 5.3 / 4.9).  nmc_k_run's eight

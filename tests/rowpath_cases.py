@@ -614,22 +614,40 @@ def environ(env):
                 os.environ[k] = v
 
 
-def gibbs_model(kind, G):
+GAUSS_SD = (0.8, 1.25, 0.6, 1.0, 0.9, 1.1, 0.7, 1.3, 0.85)
+
+
+def gibbs_model(kind, G, sizes=None, intercept=True):
+    """(family, sizes) of ``kind`` = "<family><n_fields>" over G groups: linreg (sigma = 1
+    known), linregsig (sigma sampled), logistic, gauss.  sizes: the group sizes (default: 16
+    to 32 rows, drawn); intercept: whether the design matrix of a regression or a logistic
+    model leads with the ones column (the family then has one parameter more than stored
+    covariates)."""
     r = numpy.random.RandomState(1000 + G)
-    sizes = [int(s) for s in r.randint(16, 33, size=G)]
+    drawn = [int(s) for s in r.randint(16, 33, size=G)]
+    sizes = drawn if sizes is None else [int(s) for s in sizes]
+    assert len(sizes) == G
     n = sum(sizes)
     grp = numpy.repeat(numpy.arange(G), sizes)
-    if kind == "linreg2":
+    if kind == "linreg2" and intercept:
         x = r.normal(size=n)
         b0, b1 = r.normal(size=G), r.normal(2, 1, size=G)
         y = b0[grp] + b1[grp] * x + r.normal(size=n)
         return LinearRegression.simple(x, y, sigma=1.0), sizes
-    if kind == "logistic4":
-        X = numpy.hstack([numpy.ones((n, 1)), r.normal(size=(n, 3))])
-        th = r.normal(0, 0.5, size=(G, 4))
-        p = 1 / (1 + numpy.exp(-numpy.sum(X * th[grp], axis=1)))
+    name = kind.rstrip("0123456789")
+    nf = int(kind[len(name):])
+    if name == "gauss":
+        return GaussianMean.from_groups(r.normal(size=(nf, G)), list(GAUSS_SD[:nf]), sizes), sizes
+    assert name in ("linreg", "linregsig", "logistic") and (intercept or nf >= 2), kind
+    X = numpy.hstack([numpy.ones((n, 1 if intercept else 0)), r.normal(size=(n, nf - 1))])
+    th = r.normal(0, 0.5, size=(G, X.shape[1]))
+    eta = numpy.sum(X * th[grp], axis=1)
+    if name == "logistic":
+        p = 1 / (1 + numpy.exp(-eta))
         return Logistic(X, (r.uniform(size=n) < p).astype(float)), sizes
-    return GaussianMean.from_groups(r.normal(size=(1, G)), [0.8], sizes), sizes
+    sig = 1.0 if name == "linreg" else 0.7
+    return LinearRegression(X, eta + sig * r.normal(size=n),
+                            sigma=1.0 if name == "linreg" else None), sizes
 
 
 def gibbs_mode(fam, sizes):
