@@ -349,6 +349,38 @@ int nmc_loo(nmc_ctx* ctx, int row_begin, int n_rows, int n_valid, int obs_batch,
 int nmc_psis_of(int device, const double* ll, int rows, int64_t n_obs, int C, int n_valid,
                 int obs_batch, double* elpd_i, double* lppd_i, double* k_i, int32_t* n_tail_i,
                 int64_t* nonfinite_i);
+/* LOO-PIT and the leave-one-out predictive moments (BDA3 section 7; arviz loo_pit, loo E_loo;
+ * the definitions are nestmc/loopit.py's docstring): nmc_loo's pass, whose five outputs it
+ * fills with nmc_loo's bits, and on the same sort of every batch, per response field j, the
+ * replicates of the batch in the store's layout beside the log-likelihoods (nmc_k_loo_yrep:
+ * nmc_ppc_draws' values, bit for bit) and one workgroup per observation that weights them
+ * (nmc_k_psis_expect, csrc/psis.h).  With W_s = exp(lw_s - D) the PSIS weight of sample s,
+ * tied tail samples sharing the mean weight of their places, and Z = sum_s W_s:
+ *   ess_i[i]                    Z^2 / sum_s W_s^2
+ *   wlt[i][j], weq[i][j]        sum_s W_s [y_rep_s < y] / Z and sum_s W_s [y_rep_s == y] / Z
+ *   mean[i][j], var[i][j]       sum_s W_s y_rep_s / Z and sum_s W_s (y_rep_s - mean)^2 / Z
+ *   nonfinite_draws[i][j]       the replicates that are NaN or +-inf; such a field gets NaN
+ *                               for wlt, weq, mean and var
+ * ([n_obs][NRESP] arrays, NRESP of nmc_ppc_nresp).  An observation with log-likelihoods that
+ * are not finite gets NaN everywhere.  Every sum has a fixed order: the bits depend on
+ * (n_rows, n_valid) and the tail's length alone, not on batches or row ranges; the replicates
+ * of tail samples with one log-likelihood enter in the order of their own values, so which of
+ * the tied samples carries which replicate changes no bit.  The batch's two value buffers, two
+ * key buffers, smoothed tails and tie scratch fit 1 GiB.  Argument errors are nmc_loo's;
+ * a family that cannot draw (nmc_ppc_nresp 0) and n_obs >= 2^32 also give -1.  Event slots 8
+ * and 9 bracket the kernels.                                                             */
+int nmc_loo_pit(nmc_ctx* ctx, int row_begin, int n_rows, int n_valid, int obs_batch,
+                double* elpd_i, double* lppd_i, double* k_i, int32_t* n_tail_i,
+                int64_t* nonfinite_i, double* ess_i, double* wlt, double* weq, double* mean,
+                double* var, int64_t* nonfinite_draws);
+/* The same over host arrays ll[rows][n_obs][C] and yrep[rows][n_obs][C] in the store's layout
+ * (all of their rows) and the observed values y[n_obs] of one response field (NRESP = 1),
+ * copied to `device`; needs no context.                                                  */
+int nmc_psis_expect_of(int device, const double* ll, const double* yrep, const double* y,
+                       int rows, int64_t n_obs, int C, int n_valid, int obs_batch,
+                       double* elpd_i, double* lppd_i, double* k_i, int32_t* n_tail_i,
+                       int64_t* nonfinite_i, double* ess_i, double* wlt, double* weq,
+                       double* mean, double* var, int64_t* nonfinite_draws);
 /* The rank-normalised convergence diagnostics' partial sums (Vehtari, Gelman, Simpson,
  * Carpenter, Buerkner 2021; the definitions are nestmc/rankdiag.py's docstring) over recorded
  * rows [row_begin, row_begin + n_rows) and local chains [0, n_valid), on the device from the

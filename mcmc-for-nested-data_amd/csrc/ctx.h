@@ -294,9 +294,11 @@ enum {
   NMC_OP_PREDICT = 12,     // sample rows [i0, i1), chains < nc valid, the new table ->
                            // aux = [CB][2][n_new] (m, s), out = [CB][3][NRESP][n_new],
                            // cnt = [CB][2][NRESP][n_new]; aux or out null: that pass is left out
-  NMC_OP_PREDICT_DRAWS = 13   // sample rows [i0, i1), the new table -> out = yrep
+  NMC_OP_PREDICT_DRAWS = 13,  // sample rows [i0, i1), the new table -> out = yrep
                            // [C][i1 - i0][n_new][NRESP], aux = ll [C][i1 - i0][n_new], aux2 =
                            // theta_new [C][i1 - i0][K][P]; each may be null
+  NMC_OP_LOO_YREP = 14     // NMC_OP_LOO_LL's rows and observations, response field `flags` ->
+                           // out = replicates [i1 - i0][nb][C], aux = observed values [nb]
 };
 struct NmcCall {
   int op = 0;

@@ -183,6 +183,17 @@ static int nmc_fam_call(nmc_ctx* x, const Fam& fam, NmcCall& c) {
       HIPCHK(hipGetLastError());
       return 0;
     }
+    case NMC_OP_LOO_YREP: {
+      const int n = c.i1 - c.i0;
+      if (n <= 0 || c.nb <= 0) return 0;
+      const dim3 grid((unsigned)((c.nb + 4 * NMC_LOO_OT - 1) / (4 * NMC_LOO_OT)),
+                      (unsigned)x->d.CB, (unsigned)std::min(n, 65535));
+      hipLaunchKernelGGL(nmc_k_loo_yrep<Fam>, grid, dim3(256), 0, x->stream, x->d, fam,
+                         (const int*)x->gidx, x->pooling == NMC_POOL_PARTIAL ? 2 : 0, c.i0, n,
+                         c.o0, c.nb, c.flags, c.out, c.aux);
+      HIPCHK(hipGetLastError());
+      return 0;
+    }
     case NMC_OP_OBS_LL:
       hipLaunchKernelGGL(nmc_k_obs_ll<Fam>, dim3(x->d.CB * x->G), dim3(64), 0, x->stream, x->d,
                          fam, c.in, c.out, x->n_obs);

@@ -47,3 +47,4 @@
 #include "waic.h"        // WAIC: per-observation reduction over the sample store
 #include "ppc.h"         // posterior predictive draws and their reductions over the store
 #include "predict.h"     // held-out rows and new groups: draws, densities and their reduction
+#include "loopit.h"      // LOO-PIT: one response field's replicates in the store's layout

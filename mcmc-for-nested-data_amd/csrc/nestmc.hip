@@ -15,6 +15,7 @@
 #include <algorithm>
 #include <atomic>
 #include <charconv>
+#include <functional>
 #include <chrono>
 #include <cmath>
 #include <limits>
@@ -2568,29 +2569,51 @@ static int64_t psis_batch(int64_t n_obs, int64_t S, size_t ll_bytes_per_obs, int
 // stage(o0, k, &samples, &cols, &col0): the store that holds observations [o0, o0 + k) as its
 // columns [col0, col0 + k) of cols (rows [row_begin, ...) of it are the window).
 // x: the context whose event slots 8 / 9 bracket the kernels, or NULL.
+// px (may be null): the leave-one-out expectations of nmc_loo_pit / nmc_psis_expect_of ride on
+// the same sort -- nmc_k_psis keeps its smoothed tail (lw_out), and per response field j
+// px->draw(o0, k, j, &yrep, &y) names a store of the stage's shape (cols, col0) that holds the
+// field's replicates and the batch's observed values y[k], for nmc_k_psis_expect.
+struct psis_expect {
+  int nresp = 0;
+  std::function<int(int64_t, int, int, const double**, const double**)> draw;
+  double *ess = nullptr, *wlt = nullptr, *weq = nullptr, *mean = nullptr, *var = nullptr;
+  int64_t* bad = nullptr;   // host: [n_obs] ess, [n_obs][nresp] the others
+};
 extern "C++" {
 template <class Stage>
 static int psis_run(nmc_ctx* x, hipStream_t st, int C, int row_begin, int n_rows, int n_valid,
                     int64_t n_obs, int64_t kb, int64_t M, Stage&& stage, double* elpd_i,
-                    double* lppd_i, double* k_i, int32_t* n_tail_i, int64_t* nonfinite_i) {
+                    double* lppd_i, double* k_i, int32_t* n_tail_i, int64_t* nonfinite_i,
+                    const psis_expect* px = nullptr) {
   const int64_t S = (int64_t)n_rows * n_valid;
+  const int NR = px ? px->nresp : 0;
+  double* d_lw = nullptr;    // [kb][M]: the batch's smoothed tails
+  double* d_tie = nullptr;   // [kb][3 M]: nmc_k_psis_expect's scratch for ties inside the tail
+  double* d_ex = nullptr;    // [n_obs] ess, then [4][n_obs][NR]: wlt, weq, mean, var
+  int64_t* d_xb = nullptr;   // [n_obs][NR]
+  const size_t nx = (size_t)n_obs * NR;
   uint64_t* buf[2] = {nullptr, nullptr};
   double* d_out = nullptr;   // [3][n_obs]: elpd, lppd, k
   int* d_nt = nullptr;
   int64_t* d_nf = nullptr;
   unsigned long long* d_bad = nullptr;
   const size_t lds = (size_t)M * 8;
-  hipError_t e = hipSuccess;
-  if (lds > 60 * 1024)   // (with the kernel's static 3.3 KiB: past the 64 KiB every launch may have)
-    e = hipFuncSetAttribute((const void*)nmc_k_psis, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)lds);
-  if (e == hipSuccess) e = hipMalloc(&buf[0], (size_t)kb * S * 8);
+  hipError_t e = hipMalloc(&buf[0], (size_t)kb * S * 8);
   if (e == hipSuccess) e = hipMalloc(&buf[1], (size_t)kb * S * 8);
   if (e == hipSuccess) e = hipMalloc(&d_out, (size_t)n_obs * 24);
   if (e == hipSuccess) e = hipMalloc(&d_nt, (size_t)n_obs * 4);
   if (e == hipSuccess) e = hipMalloc(&d_nf, (size_t)n_obs * 8);
   if (e == hipSuccess) e = hipMalloc(&d_bad, (size_t)n_obs * 8);
   if (e == hipSuccess) e = hipMemsetAsync(d_bad, 0, (size_t)n_obs * 8, st);
+  if (px) {
+    if (e == hipSuccess && 2 * lds > 60 * 1024)
+      e = hipFuncSetAttribute((const void*)nmc_k_psis_expect,
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2 * lds));
+    if (e == hipSuccess) e = hipMalloc(&d_lw, (size_t)kb * M * 8);
+    if (e == hipSuccess) e = hipMalloc(&d_tie, (size_t)kb * M * 24);
+    if (e == hipSuccess) e = hipMalloc(&d_ex, ((size_t)n_obs + 4 * nx) * 8);
+    if (e == hipSuccess) e = hipMalloc(&d_xb, nx * 8);
+  }
   int rc = 0;
   if (e == hipSuccess && x) rc = nmc_event_record(x, 8);
   for (int64_t o0 = 0; o0 < n_obs && e == hipSuccess && !rc; o0 += kb) {
@@ -2603,11 +2626,21 @@ static int psis_run(nmc_ctx* x, hipStream_t st, int C, int row_begin, int n_rows
     // (nmc_k_sort_tiles counts into nonfinite[col0 + j]: observation o0 + j's entry)
     e = sort_columns(st, samples, C, cols, row_begin, n_valid, S, col0, k, buf,
                      d_bad + o0 - col0, &cur);
-    if (e == hipSuccess) {
-      hipLaunchKernelGGL(nmc_k_psis, dim3((unsigned)k), dim3(NMC_PSIS_THREADS), lds, st,
+    if (e == hipSuccess)
+      e = nmc_psis_launch(st, k, lds, (const uint64_t*)buf[cur], S, (int)M,
+                          (const unsigned long long*)(d_bad + o0), d_out + o0, d_out + n_obs + o0,
+                          d_out + 2 * n_obs + o0, d_nt + o0, d_nf + o0, d_lw);
+    for (int j = 0; j < NR && e == hipSuccess && !rc; ++j) {
+      const double *yrep = nullptr, *y = nullptr;
+      rc = px->draw(o0, k, j, &yrep, &y);
+      if (rc) break;
+      double* f = d_ex + n_obs + (size_t)o0 * NR;
+      hipLaunchKernelGGL(nmc_k_psis_expect, dim3((unsigned)k), dim3(NMC_PSIS_THREADS), 2 * lds, st,
+                         samples, yrep, C, cols, row_begin, n_valid, col0,
                          (const uint64_t*)buf[cur], S, (int)M,
-                         (const unsigned long long*)(d_bad + o0), d_out + o0,
-                         d_out + n_obs + o0, d_out + 2 * n_obs + o0, d_nt + o0, d_nf + o0);
+                         (const unsigned long long*)(d_bad + o0), (const int*)(d_nt + o0),
+                         (const double*)d_lw, d_tie, y, NR, j, d_ex + o0, f, f + nx, f + 2 * nx,
+                         f + 3 * nx, d_xb + (size_t)o0 * NR);
       e = hipGetLastError();
     }
   }
@@ -2621,10 +2654,19 @@ static int psis_run(nmc_ctx* x, hipStream_t st, int C, int row_begin, int n_rows
   if (e == hipSuccess && !rc)
     e = hipMemcpyAsync(n_tail_i, d_nt, (size_t)n_obs * 4, hipMemcpyDeviceToHost, st);
   if (e == hipSuccess && !rc) e = hipMemcpyAsync(nonfinite_i, d_nf, nb, hipMemcpyDeviceToHost, st);
+  if (px) {
+    double* const host[4] = {px->wlt, px->weq, px->mean, px->var};
+    if (e == hipSuccess && !rc) e = hipMemcpyAsync(px->ess, d_ex, nb, hipMemcpyDeviceToHost, st);
+    for (int a = 0; a < 4; ++a)
+      if (e == hipSuccess && !rc)
+        e = hipMemcpyAsync(host[a], d_ex + n_obs + a * nx, nx * 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && !rc) e = hipMemcpyAsync(px->bad, d_xb, nx * 8, hipMemcpyDeviceToHost, st);
+  }
   if (e == hipSuccess && !rc) e = hipStreamSynchronize(st);
   if (e != hipSuccess) rc = fail(-2, std::string("loo: ") + hipGetErrorString(e));
   hipStreamSynchronize(st);
   hipFree(buf[0]); hipFree(buf[1]); hipFree(d_out); hipFree(d_nt); hipFree(d_nf); hipFree(d_bad);
+  hipFree(d_lw); hipFree(d_tie); hipFree(d_ex); hipFree(d_xb);
   return rc;
 }
 }  // extern "C++"
@@ -2695,6 +2737,118 @@ int nmc_psis_of(int device, const double* ll, int rows, int64_t n_obs, int C, in
   }
   hipStreamSynchronize(st);
   hipFree(dx);
+  hipStreamDestroy(st);
+  return rc;
+}
+
+// LOO-PIT and the leave-one-out predictive moments (include/nestmc.h; nestmc/loopit.py): nmc_loo
+// with a second buffer of the batch for one response field's replicates at a time
+// (nmc_k_loo_yrep), both inside the 1 GiB with the key buffers and the smoothed tails.
+int nmc_loo_pit(nmc_ctx* x, int row_begin, int n_rows, int n_valid, int obs_batch, double* elpd_i,
+                double* lppd_i, double* k_i, int32_t* n_tail_i, int64_t* nonfinite_i,
+                double* ess_i, double* wlt, double* weq, double* mean, double* var,
+                int64_t* nonfinite_draws) {
+  RES_PARK(x);
+  hipSetDevice(x->device);
+  int64_t M = 0;
+  if (int rc = psis_check(x->d.n_rows, x->C, x->n_obs, row_begin, n_rows, n_valid, obs_batch, &M))
+    return rc;
+  if (int rc = ppc_check(x)) return rc;
+  HIPCHK(hipStreamSynchronize(x->stream));
+  if (int rc = check_timeout(x)) return rc;
+  if (int rc = ensure_gidx(x)) return rc;
+  const int64_t S = (int64_t)n_rows * n_valid;
+  const size_t per_obs = (size_t)n_rows * x->C * 8;
+  const int64_t kb = psis_batch(x->n_obs, S, 2 * per_obs + (size_t)M * 32 + 8, obs_batch);
+  double *ll = nullptr, *yrep = nullptr, *yobs = nullptr;
+  hipError_t e = hipMalloc(&ll, (size_t)kb * per_obs);
+  if (e == hipSuccess) e = hipMalloc(&yrep, (size_t)kb * per_obs);
+  if (e == hipSuccess) e = hipMalloc(&yobs, (size_t)kb * 8);
+  int rc = 0;
+  if (e == hipSuccess) {
+    auto call = [&](int op, int64_t o0, int k, int j, double* out) {
+      NmcCall c;
+      c.op = op;
+      c.i0 = row_begin;
+      c.i1 = row_begin + n_rows;
+      c.o0 = o0;
+      c.nb = k;
+      c.flags = j;
+      c.out = out;
+      c.aux = yobs;
+      return nmc_call_family(x, c);
+    };
+    psis_expect px;
+    px.nresp = x->nresp;
+    px.draw = [&](int64_t o0, int k, int j, const double** yr, const double** y) {
+      *yr = yrep;   // [n_rows][k][C] beside ll
+      *y = yobs;
+      return call(NMC_OP_LOO_YREP, o0, k, j, yrep);
+    };
+    px.ess = ess_i; px.wlt = wlt; px.weq = weq; px.mean = mean; px.var = var;
+    px.bad = nonfinite_draws;
+    rc = psis_run(
+        x, x->stream, x->C, 0, n_rows, n_valid, x->n_obs, kb, M,
+        [&](int64_t o0, int k, const double** samples, int* cols, int* col0) {
+          *samples = ll;
+          *cols = k;
+          *col0 = 0;
+          return call(NMC_OP_LOO_LL, o0, k, 0, ll);
+        },
+        elpd_i, lppd_i, k_i, n_tail_i, nonfinite_i, &px);
+  } else {
+    rc = fail(-2, std::string("loo_pit: ") + hipGetErrorString(e));
+  }
+  hipFree(ll); hipFree(yrep); hipFree(yobs);
+  return rc;
+}
+
+int nmc_psis_expect_of(int device, const double* ll, const double* yrep, const double* y, int rows,
+                       int64_t n_obs, int C, int n_valid, int obs_batch, double* elpd_i,
+                       double* lppd_i, double* k_i, int32_t* n_tail_i, int64_t* nonfinite_i,
+                       double* ess_i, double* wlt, double* weq, double* mean, double* var,
+                       int64_t* nonfinite_draws) {
+  if (rows < 1 || C < 1) return fail(-1, "psis_expect_of: need rows >= 1 and C >= 1");
+  if (n_obs > 0x7fffffff) return fail(-1, "psis_expect_of: too many observations");
+  int64_t M = 0;
+  if (int rc = psis_check(rows, C, n_obs, 0, rows, n_valid, obs_batch, &M)) return rc;
+  HIPCHK(hipSetDevice(device));
+  hipStream_t st;
+  HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+  double *dx = nullptr, *dy = nullptr, *dobs = nullptr;
+  const size_t nx = (size_t)rows * n_obs * C;
+  hipError_t e = hipMalloc(&dx, nx * 8);
+  if (e == hipSuccess) e = hipMalloc(&dy, nx * 8);
+  if (e == hipSuccess) e = hipMalloc(&dobs, (size_t)n_obs * 8);
+  if (e == hipSuccess) e = hipMemcpyAsync(dx, ll, nx * 8, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(dy, yrep, nx * 8, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(dobs, y, (size_t)n_obs * 8, hipMemcpyHostToDevice, st);
+  int rc = 0;
+  if (e == hipSuccess) {
+    const int64_t kb = psis_batch(n_obs, (int64_t)rows * n_valid, (size_t)M * 32, obs_batch);
+    psis_expect px;
+    px.nresp = 1;
+    px.draw = [&](int64_t o0, int, int, const double** yr, const double** yo) {
+      *yr = dy;
+      *yo = dobs + o0;
+      return 0;
+    };
+    px.ess = ess_i; px.wlt = wlt; px.weq = weq; px.mean = mean; px.var = var;
+    px.bad = nonfinite_draws;
+    rc = psis_run(
+        nullptr, st, C, 0, rows, n_valid, n_obs, kb, M,
+        [&](int64_t o0, int, const double** samples, int* cols, int* col0) {
+          *samples = dx;
+          *cols = (int)n_obs;
+          *col0 = (int)o0;
+          return 0;
+        },
+        elpd_i, lppd_i, k_i, n_tail_i, nonfinite_i, &px);
+  } else {
+    rc = fail(-2, std::string("psis_expect_of: ") + hipGetErrorString(e));
+  }
+  hipStreamSynchronize(st);
+  hipFree(dx); hipFree(dy); hipFree(dobs);
   hipStreamDestroy(st);
   return rc;
 }

@@ -28,11 +28,12 @@ namespace {
 // (nmc_k_run: mode m (0..4) with rows in LDS at UK_RUN0 + m, rows staged at UK_RUN0 + 5 + m;
 // the half layout at UK_HALF; WAIC's reduction, waic.h, at UK_WAIC; the LL in store layout of
 // PSIS-LOO, ll_kernels.h, at UK_LOO_LL; the posterior predictive kernels, ppc.h, at UK_PPC_*;
-// the kernels of predict.h at UK_PREDICT and UK_PREDICT_DRAWS)
+// the kernels of predict.h at UK_PREDICT and UK_PREDICT_DRAWS; the replicates in store layout
+// of LOO-PIT, loopit.h, at UK_LOO_YREP)
 enum { UK_RUN0 = 0, UK_NRUN = 5, UK_GROUP_LL = 10, UK_OBS_LL_ROWS = 11, UK_OBS_LL = 12,
        UK_GROUP_LL_RL = 13, UK_GROUP_FIN = 14, UK_HALF = 15, UK_WAIC = 16, UK_LOO_LL = 17,
        UK_PPC_DRAWS = 18, UK_PPC_OBS = 19, UK_PPC_GROUP = 20, UK_PREDICT = 21,
-       UK_PREDICT_DRAWS = 22, UK_N = 23 };
+       UK_PREDICT_DRAWS = 22, UK_LOO_YREP = 23, UK_N = 24 };
 const char* const kNames[UK_N] = {
     "nmc_k_run<FamUser, 0, true>", "nmc_k_run<FamUser, 1, true>", "nmc_k_run<FamUser, 2, true>",
     "nmc_k_run<FamUser, 3, true>", "nmc_k_run<FamUser, 4, true>",
@@ -43,7 +44,7 @@ const char* const kNames[UK_N] = {
     "nmc_k_obs_ll<FamUser>", "nmc_k_group_part<FamUser, true>", "nmc_k_group_fin<FamUser>",
     "nmc_k_run<FamUser, 6, true>", "nmc_k_waic<FamUser>", "nmc_k_loo_ll<FamUser>",
     "nmc_k_ppc_draws<FamUser>", "nmc_k_ppc_obs<FamUser>", "nmc_k_ppc_group<FamUser>",
-    "nmc_k_predict<FamUser>", "nmc_k_predict_draws<FamUser>"};
+    "nmc_k_predict<FamUser>", "nmc_k_predict_draws<FamUser>", "nmc_k_loo_yrep<FamUser>"};
 int run_index(const nmc_ctx* x, int mode) {
   if (mode == NMC_MODE_HALF) return UK_HALF;
   return UK_RUN0 + mode + (x->d.rows_lds ? 0 : UK_NRUN);
@@ -384,6 +385,22 @@ int nmc_call_user(nmc_ctx* x, NmcCall& c) {
       double* out = c.out;
       void* args[] = {&dd, &fam, (void*)&gidx, &pc, &row0, &nrows, &o0, &nb, &out};
       if (int rc = user_fn(x, UK_LOO_LL, &f)) return rc;
+      return launch(x, f,
+                    dim3((unsigned)((nb + 4 * NMC_LOO_OT - 1) / (4 * NMC_LOO_OT)),
+                         (unsigned)d0.CB, (unsigned)std::min(nrows, 65535)),
+                    dim3(256), 0, args);
+    }
+    case NMC_OP_LOO_YREP: {
+      int nrows = c.i1 - c.i0, nb = c.nb;
+      if (nrows <= 0 || nb <= 0) return 0;
+      Dev dd = d0;
+      const int* gidx = (const int*)x->gidx;
+      int pc = x->pooling == NMC_POOL_PARTIAL ? 2 : 0, row0 = c.i0, j = c.flags;
+      int64_t o0 = c.o0;
+      double* out = c.out;
+      double* yobs = c.aux;
+      void* args[] = {&dd, &fam, (void*)&gidx, &pc, &row0, &nrows, &o0, &nb, &j, &out, &yobs};
+      if (int rc = user_fn(x, UK_LOO_YREP, &f)) return rc;
       return launch(x, f,
                     dim3((unsigned)((nb + 4 * NMC_LOO_OT - 1) / (4 * NMC_LOO_OT)),
                          (unsigned)d0.CB, (unsigned)std::min(nrows, 65535)),

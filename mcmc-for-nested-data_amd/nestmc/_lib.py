@@ -93,6 +93,16 @@ SIGNATURES = {
     "nmc_psis_of": (ctypes.c_int, [ctypes.c_int, _c_double_p, ctypes.c_int, ctypes.c_int64,
                                    ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_double_p,
                                    _c_double_p, _c_double_p, _c_int32_p, _c_int64_p]),
+    "nmc_loo_pit": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                   _c_double_p, _c_double_p, _c_double_p, _c_int32_p, _c_int64_p,
+                                   _c_double_p, _c_double_p, _c_double_p, _c_double_p,
+                                   _c_double_p, _c_int64_p]),
+    "nmc_psis_expect_of": (ctypes.c_int, [ctypes.c_int, _c_double_p, _c_double_p, _c_double_p,
+                                          ctypes.c_int, ctypes.c_int64, ctypes.c_int,
+                                          ctypes.c_int, ctypes.c_int, _c_double_p, _c_double_p,
+                                          _c_double_p, _c_int32_p, _c_int64_p, _c_double_p,
+                                          _c_double_p, _c_double_p, _c_double_p, _c_double_p,
+                                          _c_int64_p]),
     "nmc_rank_partials": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                          ctypes.c_int, _c_double_p, _c_double_p, _c_double_p,
                                          _c_int64_p]),

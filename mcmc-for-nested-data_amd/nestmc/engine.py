@@ -438,6 +438,56 @@ class Engine:
         return _loo.LooResult(raw["elpd"], raw["lppd"], raw["k"], raw["n_tail"],
                               raw["n_samples"], self.off)
 
+    def loo_pit_raw(self, row_begin=0, n_rows=None, n_valid=None, obs_batch=0):
+        """nmc_loo_pit as it answers, over recorded rows [row_begin, row_begin + n_rows) and
+        local chains [0, n_valid): loo_raw's dict (the same bits, from the same sort) with ess
+        [n_obs] and wlt, weq, mean, var [n_obs, NRESP] and nonfinite_draws [n_obs, NRESP]
+        (int64) of nestmc.loopit.  An observation with log-likelihoods that are not finite, or
+        a field with replicates that are not finite, has NaN results.  obs_batch as in
+        loo_raw; the results do not depend on it.  A family that cannot draw (a
+        DeviceLikelihood without nmc_user_predict) raises ValueError."""
+        if not self.family.response_fields():
+            raise ValueError("LOO-PIT needs a family that can draw from its likelihood: this "
+                             "DeviceLikelihood's source does not define nmc_user_predict")
+        if n_rows is None:
+            n_rows = self.n_rows - row_begin
+        if n_valid is None:
+            n_valid = self.C
+        n, NR = int(self.off[-1]), max(self.n_resp(), 1)
+        elpd, lppd, k, ess = (numpy.empty(n) for _ in range(4))
+        wlt, weq, mean, var = (numpy.empty((n, NR)) for _ in range(4))
+        nt = numpy.empty(n, dtype=numpy.int32)
+        bad = numpy.empty(n, dtype=numpy.int64)
+        badd = numpy.empty((n, NR), dtype=numpy.int64)
+        i64 = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))   # noqa: E731
+        check(self.lib.nmc_loo_pit(self.h, int(row_begin), int(n_rows), int(n_valid),
+                                   int(obs_batch), dptr(elpd), dptr(lppd), dptr(k),
+                                   nt.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), i64(bad),
+                                   dptr(ess), dptr(wlt), dptr(weq), dptr(mean), dptr(var),
+                                   i64(badd)))
+        return dict(elpd=elpd, lppd=lppd, k=k, n_tail=nt, nonfinite=bad, ess=ess, wlt=wlt,
+                    weq=weq, mean=mean, var=var, nonfinite_draws=badd,
+                    n_samples=int(n_rows) * int(n_valid))
+
+    def loo_pit(self, row_begin=0, n_rows=None, n_valid=None, obs_batch=0):
+        """The LooPitResult (nestmc.loopit) of this engine's chains over the given rows; its
+        .loo is the LooResult of the same pass.  A log-likelihood term or a replicate that is
+        not finite is an error."""
+        from . import loo as _loo
+        from . import loopit as _loopit
+        raw = self.loo_pit_raw(row_begin, n_rows, n_valid, obs_batch)
+        self.loo_nonfinite = int(raw["nonfinite"].sum())
+        if self.loo_nonfinite:
+            raise _lib.NestmcError("LOO-PIT: %d per-observation log-likelihood terms were not "
+                                   "finite" % self.loo_nonfinite)
+        self.loo_pit_nonfinite = int(raw["nonfinite_draws"].sum())
+        if self.loo_pit_nonfinite:
+            raise _lib.NestmcError("LOO-PIT: %d draws were not finite" % self.loo_pit_nonfinite)
+        res = _loo.LooResult(raw["elpd"], raw["lppd"], raw["k"], raw["n_tail"],
+                             raw["n_samples"], self.off)
+        return _loopit.LooPitResult(res, raw["ess"], raw["wlt"], raw["weq"], raw["mean"],
+                                    raw["var"], self.observed(), raw["nonfinite_draws"])
+
     def conv_partials(self, row_begin=0, n_rows=None, n_valid=None):
         """The convergence diagnostic's partial sums over recorded rows [row_begin, row_begin +
         n_rows) (n_rows even, two halves of n = n_rows / 2 >= 2 rows) and local chains

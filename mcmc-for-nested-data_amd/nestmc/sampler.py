@@ -28,6 +28,7 @@ from . import correlation as _correlation
 from . import groupcmp as _groupcmp
 from . import summary as _summary
 from . import loo as _loo
+from . import loopit as _loopit
 from . import rankdiag as _rankdiag
 from . import ppc as _ppc
 from . import predict as _predict
@@ -73,7 +74,7 @@ def sample_posterior(nChains, nIter, nSamples, parameterName, nGroups, nResponse
                      computeWaic=False, computeDiagnostics=False, computeSummary=False,
                      computeLoo=False, computeRankDiagnostics=False,
                      computeGroupComparison=False, computeCorrelation=False,
-                     computePredictiveChecks=False, predictFor=None):
+                     computePredictiveChecks=False, predictFor=None, computeLooPit=False):
     """Drop-in for posteriorSampling.samplePosterior (same positional/keyword API).
 
     Extra keyword-only options (all optional):
@@ -167,6 +168,17 @@ def sample_posterior(nChains, nIter, nSamples, parameterName, nGroups, nResponse
                  ranks (merged in engine and rank order: counts exactly, moments by Chan's
                  update).  A family that cannot draw (a DeviceLikelihood without
                  nmc_user_predict) raises ValueError before sampling starts
+      computeLooPit  after the loop, compute on the GPU from the device sample store the
+                 leave-one-out PIT and predictive moments of every observation (nestmc.loopit):
+                 every sample's replicate of observation i -- computePredictiveChecks' own --
+                 re-weighted by the PSIS weight of leaving i out, so that, unlike the in-sample
+                 PIT, an observation is not checked against a fit that has seen it:
+                 outputDirectory/loo_pit_pointwise.csv and loo_pit_groups.csv, "loo_pit" (a
+                 nestmc.loopit.LooPitResult; its .loo is the LooResult of the same pass) in
+                 the returned dict and one log line with the PITs outside [0.025, 0.975]
+                 against the expected 5 %.  With computeLoo as well the one pass serves both.
+                 One engine only, as computeLoo; a family that cannot draw and fewer than two
+                 samples raise ValueError before sampling starts
       predictFor  a nestmc.NewData(obs, group): rows the model was not fitted to, in the
                  family's row layout, each with a group code -- g >= 0 a training group,
                  -(k + 1) new group k, a group the model has never seen, whose values are drawn
@@ -203,6 +215,11 @@ def sample_posterior(nChains, nIter, nSamples, parameterName, nGroups, nResponse
         raise NotImplementedError(
             "computeLoo needs every chain in one engine: several devices, chains= shards and "
             "process_per_device are not supported yet")
+    if computeLooPit and ((devices is not None and len(list(devices)) > 1) or chains is not None
+                          or process_per_device or _rank is not None):
+        raise NotImplementedError(
+            "computeLooPit needs every chain in one engine: several devices, chains= shards and "
+            "process_per_device are not supported yet")
     if computeRankDiagnostics and ((devices is not None and len(list(devices)) > 1)
                                    or chains is not None or process_per_device
                                    or _rank is not None):
@@ -216,6 +233,10 @@ def sample_posterior(nChains, nIter, nSamples, parameterName, nGroups, nResponse
         raise ValueError("computePredictiveChecks needs a family that can draw from its "
                          "likelihood: this DeviceLikelihood's source does not define "
                          "nmc_user_predict (INTEGRATION.md, 'Posterior predictive checks')")
+    if computeLooPit and not logLikelihoodFunction.response_fields():
+        raise ValueError("computeLooPit needs a family that can draw from its likelihood: this "
+                         "DeviceLikelihood's source does not define nmc_user_predict "
+                         "(INTEGRATION.md, 'Posterior predictive checks')")
     if predictFor is not None:
         if not isinstance(predictFor, _predict.NewData):
             raise ValueError("predictFor must be a nestmc.NewData(obs, group)")
@@ -267,6 +288,8 @@ def sample_posterior(nChains, nIter, nSamples, parameterName, nGroups, nResponse
                              "recorded rows of all chains give %d" % n_val)
     if computeLoo and len(record_iterations(nIter, burn, thin)) * nChains < 2:
         raise ValueError("computeLoo needs at least two samples")
+    if computeLooPit and len(record_iterations(nIter, burn, thin)) * nChains < 2:
+        raise ValueError("computeLooPit needs at least two samples")
     if computePredictiveChecks and len(record_iterations(nIter, burn, thin)) * nChains < 2:
         raise ValueError("computePredictiveChecks needs at least two samples")
     if predictFor is not None and len(record_iterations(nIter, burn, thin)) * nChains < 2:
@@ -399,7 +422,8 @@ def sample_posterior(nChains, nIter, nSamples, parameterName, nGroups, nResponse
                             compute_rank=bool(computeRankDiagnostics),
                             compute_group=bool(computeGroupComparison),
                             compute_corr=bool(computeCorrelation),
-                            compute_ppc=bool(computePredictiveChecks), predict_for=predictFor)
+                            compute_ppc=bool(computePredictiveChecks), predict_for=predictFor,
+                            compute_loo_pit=bool(computeLooPit))
     finally:
         for eng, _, _ in engines:
             eng.close()
@@ -647,7 +671,7 @@ def _sample_loop(engines, nIter, burn, thin, names, G, partial, saveLogLikelihoo
                  start_time, rank_info=None, compute_waic=False, waic_dir=None,
                  n_real=None, compute_conv=False, compute_summary=False, compute_loo=False,
                  compute_rank=False, compute_group=False, compute_corr=False, compute_ppc=False,
-                 predict_for=None):
+                 predict_for=None, compute_loo_pit=False):
     """The device loop, the per-observation LL rows and the sample files of
     sample_posterior (the caller closes the engines whatever happens here).  rank_info: a
     rank of process_per_device -- this rank writes its chains' logLikelihood files, rank 0
@@ -691,8 +715,18 @@ def _sample_loop(engines, nIter, burn, thin, names, G, partial, saveLogLikelihoo
             _waic.write_csvs(waic_result, waic_dir)
 
     loo_result = None
+    loo_pit_result = None
+    if compute_loo_pit:   # (one engine, no padding chains; the one pass serves computeLoo too)
+        loo_pit_result = engines[0][0].loo_pit()
+        if write_files:
+            _loopit.write_csvs(loo_pit_result, waic_dir)
+        line = loo_pit_result.summary()
+        if logger:
+            logger.info(line)
+        if displayProgress:
+            output.print_progress(line)
     if compute_loo:   # (one engine, no padding chains: sample_posterior checked)
-        loo_result = engines[0][0].loo()
+        loo_result = loo_pit_result.loo if loo_pit_result is not None else engines[0][0].loo()
         if write_files:
             _loo.write_csvs(loo_result, waic_dir)
         warn = loo_result.warning()
@@ -789,6 +823,8 @@ def _sample_loop(engines, nIter, burn, thin, names, G, partial, saveLogLikelihoo
             res["waic"] = waic_result
         if loo_result is not None:
             res["loo"] = loo_result
+        if loo_pit_result is not None:
+            res["loo_pit"] = loo_pit_result
         if conv_result is not None:
             res["convergence"] = conv_result
         if rank_result is not None:

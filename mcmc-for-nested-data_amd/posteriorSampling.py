@@ -27,7 +27,8 @@ def samplePosterior(nChains, nIter, nSamples,
                     computeWaic=False, computeDiagnostics=False, computeSummary=False,
                     computeLoo=False, computeRankDiagnostics=False,
                     computeGroupComparison=False, computeCorrelation=False,
-                    computePredictiveChecks=False, predictFor=None, **gpu_options):
+                    computePredictiveChecks=False, predictFor=None, computeLooPit=False,
+                    **gpu_options):
     """Sample the posterior of a nested model; samples go to outputDirectory/sample/.
 
     Arguments mirror the reference (posteriorSampling.py:28-145).  Keyword-only
@@ -54,7 +55,10 @@ def samplePosterior(nChains, nIter, nSamples,
     DeviceLikelihood with nmc_user_predict, any number of engines.  predictFor=nestmc.NewData(
     obs, group) also predicts rows the model was not fitted to, of training groups and of
     groups it has never seen, on the GPU (prediction_pointwise.csv, prediction_groups.csv;
-    nestmc.predict).  Returns None like the reference unless return_samples=True.
+    nestmc.predict).  computeLooPit=True also computes the leave-one-out PIT and predictive mean
+    and sd of every observation on the GPU, its replicates re-weighted by the PSIS weights of
+    leaving it out (loo_pit_pointwise.csv, loo_pit_groups.csv; nestmc.loopit) -- a family that
+    can draw, one engine only; with computeLoo the one pass serves both.  Returns None like the reference unless return_samples=True.
     """
     return sample_posterior(nChains, nIter, nSamples, parameterName, nGroups,
                             nResponsesPerGroup, pooling, logLikelihoodFunction,
@@ -69,4 +73,4 @@ def samplePosterior(nChains, nIter, nSamples,
                             computeGroupComparison=computeGroupComparison,
                             computeCorrelation=computeCorrelation,
                             computePredictiveChecks=computePredictiveChecks,
-                            predictFor=predictFor, **gpu_options)
+                            predictFor=predictFor, computeLooPit=computeLooPit, **gpu_options)
