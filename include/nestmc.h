@@ -500,6 +500,9 @@ int nmc_variate_source(nmc_ctx* ctx, int* in_kernel);
  * the step kernel updated that launch's tasks itself, with the same results.  *out = the
  * (launch, chain block) pairs that did so since nmc_create (diagnostics and tests).     */
 int nmc_gibbs_fallbacks(nmc_ctx* ctx, int64_t* out);
+/* *separate = 1 when that Gibbs update runs as a kernel of its own (nmc_k_sweep_gibbs on a
+ * second stream), 0 when its workgroups share nmc_k_sweep's grid or another kernel runs.  */
+int nmc_gibbs_kernel(nmc_ctx* ctx, int* separate);
 
 /* Sampler._printSample (:902-905) + _print (:933-936): append rows of local
  * chain c to a CSV file with the reference's "%i,%i,%f,..." formatting (and the
@@ -555,6 +558,13 @@ int nmc_debug_varmath(int which, const double* a, const double* b, int n, double
  * lgamma, so it agrees with the device to rounding, not bit for bit.                       */
 int nmc_debug_igamci_host(const double* a, const double* q, const double* lga, int n,
                           double* out);
+/* The recording schedule without a context or a GPU.  nmc_debug_schedule_rows: the sample rows
+ * nmc_set_schedule allocates for (n_iter, burn, thin).  nmc_debug_record_rows_host: out[i] =
+ * the row iteration iter[i] is recorded in under (burn, thin, n_rows), -1 for none -- the
+ * kernels' own function (csrc/dev.h nmc_record_row) compiled for the host.                */
+int nmc_debug_schedule_rows(int n_iter, int burn, int thin, int* rows);
+int nmc_debug_record_rows_host(int burn, int thin, int n_rows, const int* iter, int n,
+                               int* out);
 /* The inverse of nmc_get_samples: writes recorded rows [row_begin, row_begin+n_rows) of the
  * device sample store from in[row][col][C] (the store as set_schedule sized it; no sampling
  * needed), so that the store's consumers -- nmc_obs_ll_rows, nmc_write_ll_csvs,

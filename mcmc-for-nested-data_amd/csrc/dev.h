@@ -162,7 +162,8 @@ __device__ __forceinline__ size_t nmc_hslot(const Dev& d, int t) {
   return (size_t)(t & 1) * d.P * d.C;
 }
 
-__device__ __forceinline__ int nmc_record_row(const Dev& d, int iter) {
+// The sample row iteration iter is recorded in, -1 for none (host: nmc_debug_record_rows_host).
+__host__ __device__ __forceinline__ int nmc_record_row(const Dev& d, int iter) {
   if (iter < d.burn) return -1;
   if (d.thin == 1) {   // (every post-burn iteration: no integer divisions on the step's path)
     const int row = iter - d.burn;

@@ -972,15 +972,21 @@ static int alloc_trace(nmc_ctx* x) {
   return 0;
 }
 
+// Sample rows of a schedule: the post-burn iterations on the thinning grid.
+static int schedule_rows(int n_iter, int burn, int thin) {
+  int rows = 0;
+  for (int i = burn; i < n_iter; ++i)
+    if (i % thin == 0) ++rows;
+  return rows;
+}
+
 int nmc_set_schedule(nmc_ctx* x, int n_iter, int burn, int thin, int tune_interval) {
   RES_PARK(x);
   hipSetDevice(x->device);
   if (n_iter < 0 || burn < 0 || burn > n_iter || thin < 1 || tune_interval < 1)
     return fail(-1, "invalid schedule");
   Dev& d = x->d;
-  int rows = 0;
-  for (int i = burn; i < n_iter; ++i)
-    if (i % thin == 0) ++rows;
+  const int rows = schedule_rows(n_iter, burn, thin);
   d.burn = burn; d.thin = thin; d.tune_interval = tune_interval; d.n_rows = rows;
   d.cols = x->P * (x->G + (x->pooling == NMC_POOL_PARTIAL ? 2 : 0));
   dfree(x, d.samples);
@@ -1511,6 +1517,12 @@ int nmc_kernel_name(nmc_ctx* x, char* out, int cap) {
                         (x->d.rows_lds ? "true" : "false") + ">";
   if (cap < 1) return fail(-1, "kernel name: cap < 1");
   snprintf(out, (size_t)cap, "%s", k.c_str());
+  return 0;
+}
+
+int nmc_gibbs_kernel(nmc_ctx* x, int* separate) {
+  if (!x || !separate) return fail(-1, "gibbs kernel: null context or output");
+  *separate = x->sweep && x->d.gsep ? 1 : 0;
   return 0;
 }
 
@@ -3122,6 +3134,23 @@ int nmc_debug_igamci_host(const double* a, const double* q, const double* lga, i
                           double* out) {
   if (n < 0) return fail(-1, "n < 0");
   for (int i = 0; i < n; ++i) out[i] = nmc_igamci(a[i], q[i], lga[i]);
+  return 0;
+}
+
+int nmc_debug_schedule_rows(int n_iter, int burn, int thin, int* rows) {
+  if (!rows) return fail(-1, "schedule rows: null output");
+  if (n_iter < 0 || burn < 0 || burn > n_iter || thin < 1) return fail(-1, "invalid schedule");
+  *rows = schedule_rows(n_iter, burn, thin);
+  return 0;
+}
+
+int nmc_debug_record_rows_host(int burn, int thin, int n_rows, const int* iter, int n,
+                               int* out) {
+  if (burn < 0 || thin < 1 || n_rows < 0 || n < 0) return fail(-1, "invalid schedule");
+  if (n > 0 && (!iter || !out)) return fail(-1, "record rows: null array");
+  Dev d{};
+  d.burn = burn; d.thin = thin; d.n_rows = n_rows;
+  for (int i = 0; i < n; ++i) out[i] = nmc_record_row(d, iter[i]);
   return 0;
 }
 

@@ -132,6 +132,7 @@ SIGNATURES = {
     "nmc_split_config": (ctypes.c_int, [_vp, _c_int_p, _c_int_p]),
     "nmc_variate_source": (ctypes.c_int, [_vp, _c_int_p]),
     "nmc_gibbs_fallbacks": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int64)]),
+    "nmc_gibbs_kernel": (ctypes.c_int, [_vp, _c_int_p]),
     "nmc_variogram": (ctypes.c_int, [ctypes.c_int, _c_double_p, ctypes.c_int, ctypes.c_int,
                                      ctypes.c_int, _c_double_p]),
     "nmc_user_family_compile": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_int, ctypes.c_int,
@@ -165,6 +166,10 @@ SIGNATURES = {
                                          _c_double_p, ctypes.c_int]),
     "nmc_debug_igamci_host": (ctypes.c_int, [_c_double_p, _c_double_p, _c_double_p, ctypes.c_int,
                                              _c_double_p]),
+    "nmc_debug_schedule_rows": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                               _c_int_p]),
+    "nmc_debug_record_rows_host": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                  _c_int_p, ctypes.c_int, _c_int_p]),
 }
 
 _lib = None

@@ -698,6 +698,13 @@ class Engine:
         check(self.lib.nmc_gibbs_fallbacks(self.h, ctypes.byref(n)))
         return n.value
 
+    def gibbs_separate(self):
+        """Whether nmc_k_sweep's Gibbs workgroups run as a kernel of their own, on a second
+        stream (nmc_gibbs_kernel), and not in the step kernel's grid."""
+        n = ctypes.c_int()
+        check(self.lib.nmc_gibbs_kernel(self.h, ctypes.byref(n)))
+        return bool(n.value)
+
     def launch_config(self):
         w, cb, pe, cl, md = (ctypes.c_int() for _ in range(5))
         check(self.lib.nmc_launch_config(self.h, ctypes.byref(w), ctypes.byref(cb),

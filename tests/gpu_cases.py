@@ -90,14 +90,19 @@ def partial_state(fam, sizes, C, P, seed=11, spread=1.0):
 
 def run_engine(fam, sizes, st, sel, chain_base, n_iter, seed, pooling="partial", priors=None,
                env=None, burn=None, thin=1, tune_interval=5, launch_iters=0, calls=None,
-               resident=False, scale=None):
+               resident=False, scale=None, sentinel=None, pre_schedules=()):
     """Run the HIP engine on chains ``sel`` of state ``st``; returns
     (accept flags [C, iter, P, G], proposal LLs, recorded rows [C, rows, cols], launch config).
     calls: the engine calls in order, ("run" | "prefill", i0, i1), ("synchronize", 0, 0),
     ("sleep", ms, 0) or ("get_state", 0, 0) (default: one run).  resident: nmc_set_resident
     (launch config: "resident" stats, "state" the final get_state, "log_prior" the final
     Engine.log_prior(), "accept" the counts).
-    scale: proposal scales [C, P, G] of all chains of ``st`` (default: the engine's ones)."""
+    scale: proposal scales [C, P, G] of all chains of ``st`` (default: the engine's ones).
+    sentinel: a uint64 bit pattern the sample store is filled with before the first call
+    (Engine.set_samples_raw), so that a row nothing wrote shows.  pre_schedules:
+    (n_iter, burn, thin) schedules set, in order, before the run's own.
+    launch config: also "n_rows" and "cols", the store set_schedule sized, and
+    "gibbs_separate" (Engine.gibbs_separate)."""
     import os
     from nestmc.engine import Engine
     old = {}
@@ -116,8 +121,13 @@ def run_engine(fam, sizes, st, sel, chain_base, n_iter, seed, pooling="partial",
     s2 = None if st.s2 is None else st.s2[sel]
     eng.set_state(st.value[sel], st.lp[sel], st.ll[sel], mu, s2,
                   scale=None if scale is None else numpy.asarray(scale)[sel])
+    for sched in pre_schedules:
+        eng.set_schedule(*sched, tune_interval=tune_interval)
     eng.set_schedule(n_iter, n_iter // 2 if burn is None else burn, thin,
                      tune_interval=tune_interval)
+    if sentinel is not None and eng.n_rows:
+        fill = numpy.full((eng.n_rows, eng.cols, eng.C), sentinel, dtype=numpy.uint64)
+        eng.set_samples_raw(fill.view(numpy.float64))
     eng.set_trace(True)
     if launch_iters:
         eng.set_launch_iters(launch_iters)
@@ -139,6 +149,8 @@ def run_engine(fam, sizes, st, sel, chain_base, n_iter, seed, pooling="partial",
     rows = eng.samples()
     cfg = eng.launch_config()
     cfg["gibbs_fallbacks"] = eng.gibbs_fallbacks()
+    cfg["n_rows"], cfg["cols"] = eng.n_rows, eng.cols
+    cfg["gibbs_separate"] = eng.gibbs_separate()
     cfg["prefill"] = eng.prefill_stats()
     cfg["resident"] = res
     cfg["state"] = eng.get_state()
@@ -159,7 +171,8 @@ def run_oracle(nested, st, sel, chain_ids, n_iter, seed, pooling="partial", prio
 def run_oracle_state(nested, st, sel, chain_ids, n_iter, seed, pooling="partial", priors=None,
                      burn=None, thin=1, tune_interval=5, scale=None):
     """run_oracle, and beside its four results the oracle's final State (of chains ``sel``)
-    and its trace dict (oracle.restatement.run)."""
+    and its trace dict (oracle.restatement.run; also "recorded": the iterations of the rows).
+    A schedule without rows gives rows of shape [C, 0, cols]."""
     from oracle import restatement as rs
     C = len(sel)
     o = rs.State(st.value[sel].copy(), st.lp[sel].copy(), st.ll[sel].copy(),
@@ -175,5 +188,7 @@ def run_oracle_state(nested, st, sel, chain_ids, n_iter, seed, pooling="partial"
     acc = numpy.stack(trace["acc"], 1).reshape(C, n_iter, P, G)
     llp = numpy.stack(trace["llp"], 1).reshape(C, n_iter, P, G)
     margin = numpy.min(numpy.stack(trace["margin"]))
-    rows = numpy.stack([r for _, r in rec], 1)
+    trace["recorded"] = [i for i, _ in rec]
+    cols = P * (G + (2 if pooling == "partial" else 0))
+    rows = numpy.stack([r for _, r in rec], 1) if rec else numpy.empty((C, 0, cols))
     return acc, llp, rows, margin, o, trace
