@@ -1572,6 +1572,13 @@ static inline void put_f(std::string& s, double v) {
   }
 }
 
+// Every write of the three writers goes through here and is checked, the intermediate flushes
+// too: a full disk is a short write (-3 with the path), never a truncated file and 0.  fclose
+// is checked by the caller; it flushes what stdio still holds.
+static inline bool put_all(FILE* f, const std::string& s) {
+  return fwrite(s.data(), 1, s.size(), f) == s.size();
+}
+
 int nmc_write_sample_csv(const char* path, int append, const char* header, const double* samples,
                          int n_chains, int c, int cols, const int32_t* row_index, int n_rows,
                          int chain_id) {
@@ -1590,9 +1597,8 @@ int nmc_write_sample_csv(const char* path, int append, const char* header, const
     }
     s += '\n';
   }
-  size_t w = fwrite(s.data(), 1, s.size(), f);
-  fclose(f);
-  if (w != s.size()) return fail(-3, std::string("short write to ") + path);
+  const bool ok = put_all(f, s);
+  if (fclose(f) != 0 || !ok) return fail(-3, std::string("short write to ") + path);
   return 0;
 }
 
@@ -2957,17 +2963,18 @@ int nmc_write_ll_csvs(nmc_ctx* x, const char* dir, const int32_t* chain_ids, int
         FILE* f = fopen(path, q.r0 == 0 ? "w" : "a");
         if (!f) { errs[tid] = std::string("cannot open ") + path; return; }
         s.clear();
-        for (int r = 0; r < q.n; ++r) {
+        bool ok = true;
+        for (int r = 0; r < q.n && ok; ++r) {
           const double* v = hb + ((size_t)k * q.n + r) * n_obs;
           for (int64_t i = 0; i < n_obs; ++i) {
             if (i) s += ',';
             put_f(s, v[i]);
           }
           s += '\n';
-          if (s.size() > (1u << 22)) { fwrite(s.data(), 1, s.size(), f); s.clear(); }
+          if (s.size() > (1u << 22)) { ok = put_all(f, s); s.clear(); }
         }
-        const size_t w = fwrite(s.data(), 1, s.size(), f);
-        if (fclose(f) != 0 || w != s.size()) { errs[tid] = std::string("short write to ") + path; return; }
+        if (ok) ok = put_all(f, s);
+        if (fclose(f) != 0 || !ok) { errs[tid] = std::string("short write to ") + path; return; }
       }
     };
     std::vector<std::thread> pool;
@@ -2986,16 +2993,17 @@ int nmc_write_ll_csv(const char* path, int append, const double* ll, int64_t n, 
   FILE* f = fopen(path, append ? "a" : "w");
   if (!f) return fail(-3, std::string("cannot open ") + path);
   std::string s;
-  for (int r = 0; r < n_rows; ++r) {
+  bool ok = true;
+  for (int r = 0; r < n_rows && ok; ++r) {
     for (int64_t k = 0; k < n; ++k) {
       if (k) s += ',';
       put_f(s, ll[(size_t)r * n + k]);
     }
     s += '\n';
-    if (s.size() > (1u << 24)) { fwrite(s.data(), 1, s.size(), f); s.clear(); }
+    if (s.size() > (1u << 24)) { ok = put_all(f, s); s.clear(); }
   }
-  fwrite(s.data(), 1, s.size(), f);
-  fclose(f);
+  if (ok) ok = put_all(f, s);
+  if (fclose(f) != 0 || !ok) return fail(-3, std::string("short write to ") + path);
   return 0;
 }
 

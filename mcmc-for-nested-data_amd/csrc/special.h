@@ -70,8 +70,12 @@ __device__ inline double nmc_prior_logpdf(int fam, const double* prm, double x) 
     case NMC_PRIOR_HALFNORM:
       if (!(y >= 0.0)) return ninf;
       return (0.5 * log(2.0 / 3.141592653589793) - y * y / 2.0) - ls;
-    case NMC_PRIOR_CAUCHY:
-      return (-NMC_LOG_PI - log1p(y * y)) - ls;
+    case NMC_PRIOR_CAUCHY: {           // scipy's two branches: y * y overflows from 2^512 on
+      const double ay = fabs(y);
+      if (ay < 1.0) return (-NMC_LOG_PI - log1p(ay * ay)) - ls;
+      const double ry = 1.0 / ay;
+      return (-NMC_LOG_PI - (2.0 * log(ay) + log1p(ry * ry))) - ls;
+    }
     case NMC_PRIOR_LAPLACE:
       return log(0.5 * exp(-fabs(y))) - ls;
     case NMC_PRIOR_LOGNORM: {          // scipy _lognorm_logpdf, open support

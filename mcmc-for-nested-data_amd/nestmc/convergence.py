@@ -135,16 +135,19 @@ def finish(vg, mean, m2, n, names, n_valid=None):
                              numpy.sqrt(vhat), V, T, n, m)
 
 
-def variogram_host(x):
-    """nestmc.diagnosis.variogram's numbers on the host (its order: rows ascending inside a
-    half-chain, the half-chains' sums in j order, one division): x [K][m][n] -> V [K][n]."""
+def variogram_host(x, lags=None):
+    """nestmc.diagnosis.variogram's numbers on the host, bit for bit (its order: rows ascending
+    inside a half-chain, the half-chains' sums in j order, one division): x [K][m][n] -> V [K][n],
+    or V [K][len(lags)] at the given lags only."""
     x = numpy.asarray(x, dtype=numpy.float64)
     K, m, n = x.shape
-    V = numpy.zeros((K, n))
-    for t in range(1, n):
-        d = x[:, :, t:] - x[:, :, :n - t]
-        s = numpy.cumsum(d * d, axis=2)[:, :, -1]
-        V[:, t] = numpy.cumsum(s, axis=1)[:, -1] / (float(m) * float(n - t))
+    lags = range(n) if lags is None else [int(t) for t in lags]
+    V = numpy.zeros((K, len(lags)))
+    with numpy.errstate(invalid="ignore", over="ignore"):
+        for i, t in enumerate(lags):   # lag 0 like every other: inf - inf = NaN, as on the device
+            d = x[:, :, t:] - x[:, :, :n - t]
+            s = numpy.cumsum(d * d, axis=2)[:, :, -1]
+            V[:, i] = numpy.cumsum(s, axis=1)[:, -1] / (float(m) * float(n - t))
     return V
 
 

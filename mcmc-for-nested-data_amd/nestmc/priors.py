@@ -26,6 +26,10 @@ def encode(dist):
         raise ValueError("unexpected shape parameters for %s" % name)
     loc = float(loc)
     scale = float(scale)
+    if numpy.isnan(shape):
+        # scipy gives NaN at every x for a NaN shape, outside the support too; the device
+        # tests the support first, so the bad argument travels as a NaN scale
+        scale = float("nan")
     with numpy.errstate(all="ignore"):
         lga = float(scipy.special.gammaln(shape)) if name in ("gamma", "invgamma") else 0.0
         ls = float(numpy.log(scale))

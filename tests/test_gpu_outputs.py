@@ -113,3 +113,30 @@ def test_ll_csvs_chain_batched_branch_byte_identical(gpu_lib, tmp_path, monkeypa
         b = (many / ("logLikelihood.%d.csv" % c)).read_bytes()
         assert a == b and a.count(b"\n") == eng.n_rows, c
     eng.close()
+
+
+def test_ll_csvs_per_chain_flush_byte_identical(gpu_lib, tmp_path, monkeypatch):
+    """nmc_write_ll_csvs's flush inside one chain's file (more than 4 MiB of text pending): a
+    complete-pooling engine with 6 000 observations, 2 chains and 80 recorded rows writes
+    about 4.8 MB per chain in one batch, so the flush is taken and a tail follows it.  Each
+    file equals "%f" of obs_ll_rows() byte for byte."""
+    fam, sizes, priors, pooling, names = synthetic("linreg_complete", 2, 1, 6000)
+    value, lp, ll, mu, s2, _ = _state(fam, sizes, 2, fam.n_params, pooling)
+    eng = Engine(fam, sizes, 2, pooling, priors, seed=6)
+    eng.set_state(value, lp, ll, mu, s2)
+    eng.set_schedule(80, 0, 1)
+    eng.run(0, 80)
+    eng.synchronize()
+    got = eng.obs_ll_rows()
+    assert got.shape == (2, eng.n_rows, 6000) and eng.n_rows >= 75
+    monkeypatch.delenv("NMC_LL_BATCH_BYTES", raising=False)     # one batch of all rows
+    ids = [3, 11]
+    eng.write_ll_csvs(str(tmp_path), ids, threads=2)
+    for c in range(2):
+        lines = [",".join("%f" % v for v in row) + "\n" for row in got[c]]
+        want = "".join(lines).encode()
+        pending = numpy.cumsum([len(s) for s in lines])
+        assert pending[-2] > (1 << 22), "the flush must be taken, and before the last row"
+        data = (tmp_path / ("logLikelihood.%d.csv" % ids[c])).read_bytes()
+        assert data == want, (c, len(data), len(want))
+    eng.close()
