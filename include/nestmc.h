@@ -572,6 +572,18 @@ int nmc_debug_record_rows_host(int burn, int thin, int n_rows, const int* iter, 
  * nmc_rank_partials -- can be run
  * on rows a sampler would not produce.  Nothing in the product path calls it.           */
 int nmc_debug_set_samples(nmc_ctx* ctx, int row_begin, int n_rows, const double* in);
+/* The plan nmc_run works to, for tests that run with variate buffers shorter than the run
+ * (NMC_VARIATE_BYTES).  nmc_debug_variate_plan (after nmc_set_schedule): vcap, the iterations
+ * one variate buffer holds; chunk, the iterations of one step launch (nmc_set_launch_iters,
+ * at most vcap); counter_wrap, the limit in force below.  Any output may be NULL.
+ * nmc_debug_set_counter_wrap: the counters that run on across launches (publishes, hyper-ready
+ * counts, row-split arrivals) are zeroed before groups * iterations or members * steps since
+ * the last reset would reach the limit, 2^31 by default; a lower limit (1 .. 2^31, else -1)
+ * makes that reset run within a short run.  It changes no result.
+ * nmc_debug_counter_resets: the resets so far.  Nothing in the product path calls these.  */
+int nmc_debug_variate_plan(nmc_ctx* ctx, int* vcap, int* chunk, int64_t* counter_wrap);
+int nmc_debug_set_counter_wrap(nmc_ctx* ctx, int64_t limit);
+int nmc_debug_counter_resets(nmc_ctx* ctx, int64_t* resets);
 /* Diagnostic build only (make stamps -> libnestmc_stamps.so): shader-clock phase
  * stamps of the step kernel, [2 blocks][2 waves][8 iterations][16 slots]; n > 0
  * arms (zeroes) the buffer, out != NULL copies it back.  Error in the shipped lib. */

@@ -69,6 +69,10 @@ struct nmc_ctx {
   int prefill_bpc = 1;                    // prefill grid: blocks per CU (beside a step kernel)
   bool prefill_on = true;                 // pipelined fill (NMC_PREFILL=0: off, the A/B)
   long long pf_issued = 0, pf_used = 0;   // iterations prefilled / consumed from a prefill
+  // Dev.cnt / hrd / xcnt are reset before G * pbase or S * xbase would reach this (nmc_run,
+  // res_continue); tests lower it (nmc_debug_set_counter_wrap) so that the reset runs
+  uint64_t counter_wrap = 1ull << 31;
+  long long counter_resets = 0;           // resets so far (nmc_debug_counter_resets)
   int C = 0, chain_base = 0, G = 0, P = 0, pooling = 0, family = 0, nf = 0, rng = 0;
   uint32_t seed = 0;
   int64_t n_obs = 0;

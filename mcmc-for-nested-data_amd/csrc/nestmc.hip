@@ -493,8 +493,8 @@ static int res_continue(nmc_ctx* x, int i0, int i1) {
   const int why = i0 != r.end ? 1 : x->ktiming ? 2 : i1 - i0 > fill_chunk(x) ? 3
                 : i1 - r.vbase > x->d.vcap ? 4
                 : !(x->pf.valid && x->pf.buf == r.buf && x->pf.i0 == i0 && x->pf.i1 >= i1) ? 5
-                : ((uint64_t)x->G * (x->d.pbase + (uint64_t)(i1 - i0)) >= (1ull << 31) ||
-                   (uint64_t)x->d.S * (x->d.xbase + (uint64_t)(i1 - i0) * x->P) >= (1ull << 31))
+                : ((uint64_t)x->G * (x->d.pbase + (uint64_t)(i1 - i0)) >= x->counter_wrap ||
+                   (uint64_t)x->d.S * (x->d.xbase + (uint64_t)(i1 - i0) * x->P) >= x->counter_wrap)
                     ? 6 : 0;
   if (why) {
     r.why = why;
@@ -1128,14 +1128,15 @@ int nmc_run(nmc_ctx* x, int iter_begin, int iter_end) {
       // counters continue from the earlier launches (Dev.pbase / xbase): reset only
       // before they could wrap
       const uint64_t steps = (uint64_t)(c1 - c0) * P;
-      if ((uint64_t)x->G * (x->d.pbase + (uint64_t)(c1 - c0)) >= (1ull << 31) ||
-          (uint64_t)x->d.S * (x->d.xbase + steps) >= (1ull << 31)) {
+      if ((uint64_t)x->G * (x->d.pbase + (uint64_t)(c1 - c0)) >= x->counter_wrap ||
+          (uint64_t)x->d.S * (x->d.xbase + steps) >= x->counter_wrap) {
         HIPCHK(hipMemsetAsync(x->d.cnt, 0, cnt_bytes(x), x->stream));
         HIPCHK(hipMemsetAsync(x->d.hrd, 0, hrd_words(x) * sizeof(unsigned), x->stream));
         if (x->d.xcnt)
           HIPCHK(hipMemsetAsync(x->d.xcnt, 0, (size_t)x->d.RB * x->d.G * 32 * sizeof(unsigned),
                                 x->stream));
         x->d.pbase = x->d.xbase = 0;
+        x->counter_resets += 1;
       }
       // a one-chunk call of a resident context: the resident instance, which then takes the
       // following calls (res_continue)
@@ -3120,6 +3121,28 @@ int nmc_debug_set_samples(nmc_ctx* x, int row_begin, int n_rows, const double* i
   if (n_rows)
     HIPCHK(hipMemcpy(d.samples + (size_t)row_begin * per, in, (size_t)n_rows * per * 8,
                      hipMemcpyHostToDevice));
+  return 0;
+}
+
+// What nmc_run plans with (tests only): iterations per variate buffer, iterations per step
+// launch, and the limit the launch-spanning counters are reset before
+int nmc_debug_variate_plan(nmc_ctx* x, int* vcap, int* chunk, int64_t* counter_wrap) {
+  if (!x->scheduled) return fail(-1, "nmc_set_schedule first");
+  if (vcap) *vcap = x->d.vcap;
+  if (chunk) *chunk = fill_chunk(x);
+  if (counter_wrap) *counter_wrap = (int64_t)x->counter_wrap;
+  return 0;
+}
+
+int nmc_debug_set_counter_wrap(nmc_ctx* x, int64_t limit) {
+  if (limit < 1 || limit > ((int64_t)1 << 31))
+    return fail(-1, "counter wrap limit outside 1..2^31");
+  x->counter_wrap = (uint64_t)limit;
+  return 0;
+}
+
+int nmc_debug_counter_resets(nmc_ctx* x, int64_t* resets) {
+  if (resets) *resets = x->counter_resets;
   return 0;
 }
 

@@ -170,6 +170,9 @@ SIGNATURES = {
                                                _c_int_p]),
     "nmc_debug_record_rows_host": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                   _c_int_p, ctypes.c_int, _c_int_p]),
+    "nmc_debug_variate_plan": (ctypes.c_int, [_vp, _c_int_p, _c_int_p, _c_int64_p]),
+    "nmc_debug_set_counter_wrap": (ctypes.c_int, [_vp, ctypes.c_int64]),
+    "nmc_debug_counter_resets": (ctypes.c_int, [_vp, _c_int64_p]),
 }
 
 _lib = None

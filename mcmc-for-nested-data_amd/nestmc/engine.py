@@ -161,6 +161,24 @@ class Engine:
         return {"enabled": bool(e.value), "active": bool(a.value), "launches": n.value,
                 "calls": c.value, "last_refusal": w.value}
 
+    def variate_plan(self):
+        """Verification hook: {"vcap": iterations one variate buffer holds, "chunk":
+        iterations per step launch, "counter_wrap": the limit of set_counter_wrap,
+        "counter_resets": resets so far} (nmc_debug_variate_plan, nmc_debug_counter_resets)."""
+        v, c = ctypes.c_int(), ctypes.c_int()
+        w, n = ctypes.c_int64(), ctypes.c_int64()
+        check(self.lib.nmc_debug_variate_plan(self.h, ctypes.byref(v), ctypes.byref(c),
+                                              ctypes.byref(w)))
+        check(self.lib.nmc_debug_counter_resets(self.h, ctypes.byref(n)))
+        return {"vcap": v.value, "chunk": c.value, "counter_wrap": w.value,
+                "counter_resets": n.value}
+
+    def set_counter_wrap(self, limit):
+        """Verification hook (nmc_debug_set_counter_wrap): reset the counters that run on
+        across launches before they would reach ``limit`` (1 .. 2**31, the default), so that
+        a short run meets the reset.  No effect on results; no product path calls this."""
+        check(self.lib.nmc_debug_set_counter_wrap(self.h, int(limit)))
+
     # -- results --------------------------------------------------------------
     def samples_raw(self, row_begin=0, n_rows=None):
         """[rows][cols][C] exactly as stored on the device."""

@@ -90,7 +90,8 @@ def partial_state(fam, sizes, C, P, seed=11, spread=1.0):
 
 def run_engine(fam, sizes, st, sel, chain_base, n_iter, seed, pooling="partial", priors=None,
                env=None, burn=None, thin=1, tune_interval=5, launch_iters=0, calls=None,
-               resident=False, scale=None, sentinel=None, pre_schedules=()):
+               resident=False, scale=None, sentinel=None, pre_schedules=(), schedule_env=None,
+               counter_wrap=None, log_calls=False):
     """Run the HIP engine on chains ``sel`` of state ``st``; returns
     (accept flags [C, iter, P, G], proposal LLs, recorded rows [C, rows, cols], launch config).
     calls: the engine calls in order, ("run" | "prefill", i0, i1), ("synchronize", 0, 0),
@@ -102,8 +103,28 @@ def run_engine(fam, sizes, st, sel, chain_base, n_iter, seed, pooling="partial",
     (Engine.set_samples_raw), so that a row nothing wrote shows.  pre_schedules:
     (n_iter, burn, thin) schedules set, in order, before the run's own.
     launch config: also "n_rows" and "cols", the store set_schedule sized, and
-    "gibbs_separate" (Engine.gibbs_separate)."""
+    "gibbs_separate" (Engine.gibbs_separate).
+    schedule_env: environment set around the set_schedule calls alone (nmc_set_schedule reads
+    NMC_VARIATE_BYTES at every call).  counter_wrap: Engine.set_counter_wrap before the first
+    call.  log_calls: launch config "log", one {"resident", "prefill", "counter_resets"} per
+    entry of ``calls`` as they stood when it returned.  launch config: also "variate_plan"
+    (Engine.variate_plan after the last call)."""
+    import contextlib
     import os
+
+    @contextlib.contextmanager
+    def _environ(e):
+        was = {k: os.environ.get(k) for k in e}
+        os.environ.update(e)
+        try:
+            yield
+        finally:
+            for k, v in was.items():
+                if v is None:
+                    os.environ.pop(k)
+                else:
+                    os.environ[k] = v
+
     from nestmc.engine import Engine
     old = {}
     for k, v in (env or {}).items():
@@ -121,10 +142,11 @@ def run_engine(fam, sizes, st, sel, chain_base, n_iter, seed, pooling="partial",
     s2 = None if st.s2 is None else st.s2[sel]
     eng.set_state(st.value[sel], st.lp[sel], st.ll[sel], mu, s2,
                   scale=None if scale is None else numpy.asarray(scale)[sel])
-    for sched in pre_schedules:
-        eng.set_schedule(*sched, tune_interval=tune_interval)
-    eng.set_schedule(n_iter, n_iter // 2 if burn is None else burn, thin,
-                     tune_interval=tune_interval)
+    with _environ(schedule_env or {}):
+        for sched in pre_schedules:
+            eng.set_schedule(*sched, tune_interval=tune_interval)
+        eng.set_schedule(n_iter, n_iter // 2 if burn is None else burn, thin,
+                         tune_interval=tune_interval)
     if sentinel is not None and eng.n_rows:
         fill = numpy.full((eng.n_rows, eng.cols, eng.C), sentinel, dtype=numpy.uint64)
         eng.set_samples_raw(fill.view(numpy.float64))
@@ -133,6 +155,9 @@ def run_engine(fam, sizes, st, sel, chain_base, n_iter, seed, pooling="partial",
         eng.set_launch_iters(launch_iters)
     if resident:
         eng.set_resident(True)
+    if counter_wrap is not None:
+        eng.set_counter_wrap(counter_wrap)
+    log = []
     for op, a, b in calls or [("run", 0, n_iter)]:
         if op == "synchronize":
             eng.synchronize()
@@ -143,6 +168,9 @@ def run_engine(fam, sizes, st, sel, chain_base, n_iter, seed, pooling="partial",
             eng.get_state()
         else:
             getattr(eng, op)(a, b)
+        if log_calls:
+            log.append({"resident": eng.resident_stats(), "prefill": eng.prefill_stats(),
+                        "counter_resets": eng.variate_plan()["counter_resets"]})
     eng.synchronize()
     res = eng.resident_stats()
     acc, llp = eng.trace(n_iter)
@@ -156,6 +184,8 @@ def run_engine(fam, sizes, st, sel, chain_base, n_iter, seed, pooling="partial",
     cfg["state"] = eng.get_state()
     cfg["log_prior"] = eng.log_prior()
     cfg["accept"] = eng.accept_counts()
+    cfg["variate_plan"] = eng.variate_plan()
+    cfg["log"] = log
     eng.close()
     return acc, llp, rows, cfg
 
